@@ -20,6 +20,15 @@ The timed region excludes inference and file I/O, as the reference's "Search tim
 (src/main.cpp:272-285); the encoder, the L2 rerank and the PCIe-inclusive host path are reported beside it.
 `--sw-band W` adds the opt-in banded SW rerank (not parity with the reference) on the same search rows as
 `sw_band_opt_in`; the headline is always the full DP.
+
+A plain run does what the headline needs and no more: workload (from the cache when it is there; `--prepare-only`
+fills the cache and exits), warm-up, the timed steps, the sanity checks of the last step, the result line with
+the per-kernel event times of the timed steps. `--full` adds everything measured or checked beside the headline,
+each in runs of its own: the exact-statistics search and the rooflines priced with it, truth recall, the live
+latency probe, the host path, the encoder, the L2 rerank, `--sw-band`, the CPU baseline, C4's k = 5 run.
+`--dump-outputs DIR` writes what the last timed step left in the caller's buffers as DIR/<name>.npy (float32, or
+float64 for integers), a fixed seeded sample of rows where the whole would pass DUMP_BYTES; the workload is
+seeded, so two runs with the same arguments dump the same arrays.
 """
 import argparse
 import json
@@ -114,6 +123,30 @@ def _claim_stdout():
     sys.stdout.flush()
     _RESULT_OUT = os.fdopen(os.dup(1), "w")
     os.dup2(2, 1)
+
+
+DUMP_BYTES = 48 << 20  # --dump-outputs writes at most this much in all (the files' headers aside)
+DUMP_SEED = 20
+
+
+def dump_outputs(out_dir, bufs):
+    """--dump-outputs: the device buffers the timed path filled in its last step ([(name, DeviceBuffer)], one row
+    per read), as out_dir/<name>.npy. float32 stays float32; integers (labels up to 5e7, counts) become float64,
+    which holds them exactly. When all rows would pass DUMP_BYTES the same seeded sample of rows, ascending, is
+    taken from every buffer, and rows.npy names them."""
+    n = bufs[0][1].shape[0]
+    as_type = {name: np.float32 if b.dtype == np.float32 else np.float64 for name, b in bufs}
+    row_bytes = 8 + sum(int(np.prod(b.shape[1:], dtype=np.int64)) * np.dtype(as_type[name]).itemsize
+                        for name, b in bufs)
+    rows = np.arange(n)
+    if n * row_bytes > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_BYTES // row_bytes, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float64))
+    for name, b in bufs:
+        assert b.shape[0] == n, (name, b.shape)
+        np.save(os.path.join(out_dir, name + ".npy"), b.download_rows(rows).astype(as_type[name]))
+    log(f"[bench] --dump-outputs: {len(rows)} of {n} rows of {', '.join(name for name, _ in bufs)} in {out_dir}")
 
 
 class Dist:
@@ -432,6 +465,33 @@ def dep_load_latency(dev, waves, footprint=16 << 30, hops=2000):
                              f"384-B row loads over {footprint >> 30} GB")
 
 
+def default_cache():
+    """The workload cache (C5: 7.5 GB of windows + a 7 GB index). It lives under the home directory, which a box
+    keeps from build() -- whose `--prepare-only` run fills it -- to every later run; the temp dir does not last as
+    long. Without a writable home it is the temp dir after all."""
+    import tempfile
+    if os.environ.get("DRM_BENCH_CACHE"):
+        return os.environ["DRM_BENCH_CACHE"]
+    path = os.path.join(os.path.expanduser("~"), ".cache", "deepreadmapper_amd", "bench")
+    try:
+        os.makedirs(path, exist_ok=True)
+        if os.access(path, os.W_OK):
+            return path
+    except OSError:
+        pass
+    return os.path.join(tempfile.gettempdir(), "drm_bench_cache")
+
+
+def gpu_present():
+    """Is there a device to build the workload on? (hipGetDeviceCount fails outright on a box without one.)"""
+    from deepreadmapper_amd._native import DrmError
+    from deepreadmapper_amd.device import device_count
+    try:
+        return device_count() > 0
+    except DrmError:
+        return False
+
+
 def comm_unique_id(D):
     """Rank 0's RCCL unique id, broadcast over the gloo control plane (None if it failed, or if rank 0's
     communicator exists already). Collective, whatever state a rank is in: every rank calls it at the same point."""
@@ -588,6 +648,8 @@ def run_c4(args, D):
     D.barrier()
     if D.rank != 0:
         w.generate(args.cache, need_refs=False, gpu_build=True)
+    if args.prepare_only:
+        return D.close()
     lo, hi = shard_range(N * Q, D.rank, N)
     q_emb = np.ascontiguousarray(w.q_emb[lo:hi])
     ix = HnswPqIndex(w.index_path, D.local_rank % max(ndev, 1))
@@ -595,7 +657,7 @@ def run_c4(args, D):
     d_x = DeviceBuffer.from_host(q_emb)
     stream = Stream()
     runs = {}
-    for K in (args.k, 5):
+    for K in ((args.k, 5) if args.full else (args.k,)):  # k = 5 is a configuration beside the headline's
         d_D, d_I = DeviceBuffer((Q, K), np.float32), DeviceBuffer((Q, K), np.int64)
         d_nd, d_nh, d_nu = DeviceBuffer(Q, np.int32), DeviceBuffer(Q, np.int32), DeviceBuffer(Q, np.int32)
         for _ in range(args.warmup):
@@ -613,6 +675,12 @@ def run_c4(args, D):
         synchronize()
         el = D.allreduce(time.perf_counter() - t0, "MAX")
         ms = float(np.mean([e[0].elapsed_ms(e[1]) for e in ev]))
+        if args.dump_outputs and D.rank == 0 and K == args.k:
+            dump_outputs(args.dump_outputs, [("search_dists", d_D), ("search_ids", d_I), ("ndis", d_nd),
+                                             ("nhops", d_nh), ("nhops_upper", d_nu)])
+        if not args.full:
+            runs[K] = {"value": N * Q * args.steps / el, "ms": ms}
+            continue
         # faiss's ndis for the algorithmic bytes: one untimed exact-statistics search (see main())
         ix.set_exact_stats(True)
         ix.search_device(d_x, Q, K, args.ef, d_D, d_I, d_nd, d_nh, stream, d_nhops_upper=d_nu)
@@ -625,7 +693,7 @@ def run_c4(args, D):
         runs[K] = {"value": N * Q * args.steps / el, "ms": ms, "ndis": float(ndis.mean()), "nhops": float(nhops.mean()),
                    "achieved": bl / (ms * 1e-3) / 1e9}
     cpu = None
-    if D.rank == 0 and N == 1 and not args.no_cpu:
+    if D.rank == 0 and N == 1 and args.full and not args.no_cpu:
         from oracle import faiss_file, oracle as O
         threads = int(os.environ.get("OMP_NUM_THREADS", "0")) or len(os.sched_getaffinity(0))
         threads = max(1, min(threads, len(os.sched_getaffinity(0))))
@@ -652,13 +720,14 @@ def run_c4(args, D):
                                    f"{info.ntotal} windows (M_pq=8 nbits=8 M_hnsw=16 EFC=200, GPU-built), search only",
                        "n_refs": int(info.ntotal), "queries_per_gpu": Q, "ef": args.ef, "k": args.k,
                        "parallelism": f"dp{N} (query shards, index replicated per GPU)"},
-            "roofline": {"bound": "hbm", "kernel": SEARCH_KERNEL, "achieved": round(r["achieved"], 2),
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(r["achieved"] / HBM_PEAK_GBS, 5),
-                         "traffic": None, "avg_launch_ms": round(r["ms"], 4)},
-            "cpu_baseline": cpu,
-            "k5": {"value": round(runs[5]["value"], 1), "ms": round(runs[5]["ms"], 3),
-                   "achieved_gbs": round(runs[5]["achieved"], 2)},
-            "breakdown": {"ndis_mean": round(r["ndis"], 1), "nhops_mean": round(r["nhops"], 1)},
+            **({"breakdown": {"search_ms": round(r["ms"], 3)}} if not args.full else {
+                "roofline": {"bound": "hbm", "kernel": SEARCH_KERNEL, "achieved": round(r["achieved"], 2),
+                             "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(r["achieved"] / HBM_PEAK_GBS, 5),
+                             "traffic": None, "avg_launch_ms": round(r["ms"], 4)},
+                "cpu_baseline": cpu,
+                "k5": {"value": round(runs[5]["value"], 1), "ms": round(runs[5]["ms"], 3),
+                       "achieved_gbs": round(runs[5]["achieved"], 2)},
+                "breakdown": {"ndis_mean": round(r["ndis"], 1), "nhops_mean": round(r["nhops"], 1)}}),
         })
     D.close()
 
@@ -705,7 +774,17 @@ def main():
     ap.add_argument("--queries", type=int, default=0, help="reads per GPU (weak scaling); 0 = the workload's own")
     ap.add_argument("--ef", type=int, default=128)
     ap.add_argument("--k", type=int, default=128)
-    ap.add_argument("--cache", default=os.environ.get("DRM_BENCH_CACHE", "/tmp/drm_bench_cache"))
+    ap.add_argument("--cache", default=None,
+                    help="where the workload's window table and index files are kept between runs: $DRM_BENCH_CACHE, "
+                         "else ~/.cache/deepreadmapper_amd/bench (the temp dir without a writable home)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what stands beside the headline, in runs of their own: exact search "
+                         "statistics and the rooflines, truth recall, host path, encoder, L2 rerank, --sw-band, the CPU "
+                         "baseline, C4's k = 5 (the --no-* options below drop single legs of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--prepare-only", action="store_true",
+                    help="build what the workload keeps in --cache (window table, index), then exit without a result")
     ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of oracle CPU work")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-host-path", action="store_true", help="skip the pinned-host drm_search_rerank timing")
@@ -737,6 +816,12 @@ def main():
         args.embed = "gru" if args.workload == "c5" else "kmer3"
     if args.embed == "gru" and (args.workload != "c5" or args.index != "pq"):
         raise SystemExit("--embed gru builds the C5 PQ index only")
+    if args.sw_band and not args.full:
+        raise SystemExit("--sw-band is a leg of --full")
+    if args.prepare_only and not gpu_present():
+        log("[bench] --prepare-only: no GPU here (the index is built on one), nothing prepared")
+        return D.close()
+    args.cache = args.cache or default_cache()
     if args.workload == "c4":
         return run_c4(args, D)
     from deepreadmapper_amd import synth
@@ -770,6 +855,9 @@ def main():
             os.replace(fpath + ".tmp", fpath)
             log(f"[bench] hnswlib fp32 index built in {time.time() - t0:.1f}s")
         D.barrier()
+    if args.prepare_only:
+        return D.close()
+    if flat:
         ix = HnswFlatIndex(fpath, dev)
         replication = {"mode": "file per rank", "why": "hnswlib index"}
         d_L = DeviceBuffer((Q, K), np.uint64)
@@ -837,6 +925,42 @@ def main():
     ndis, nhops, nup = d_nd.download().astype(np.int64), d_nh.download().astype(np.int64), d_nu.download()
     if (nhops < 0).any():
         raise SystemExit(f"{int((nhops < 0).sum())} queries ended on the search's hop bound")
+    if args.dump_outputs and D.rank == 0:
+        dump_outputs(args.dump_outputs, [("search_dists", d_D), ("search_ids", d_L if flat else d_I), ("ndis", d_nd),
+                                         ("nhops", d_nh), ("nhops_upper", d_nu), ("sw_scores", d_sc), ("sw_ids", d_id),
+                                         ("sw_status", d_st)])
+    total_reads = float(N * Q * args.steps)
+    value = total_reads / elapsed_max
+    headline = {
+        "metric": "mapped reads/sec, 150 bp queries, EF=128 K=128",
+        "value": round(value, 1), "unit": "reads/s", "n_gpus": N, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed_max / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": ("fp32 (L2 distances)" if flat else "fp32 (PQ-ADC distances)") + (
+            " + int32 (SW DP, bit-profile u16 kernel)" if os.environ.get("DRM_SW_BITPROFILE") == "1" else
+            " + u16 integer SW DP (two cells per register)"),
+        "data": f"synthetic (seeded genome/reads, {EMBED_DESC[args.embed]} embeddings; no network)",
+        "config": {"workload": wl["desc"] if not flat else (
+                       "C3-flat: the same 1M windows in an hnswlib fp32-L2 index (M=64, EFC=128), hnswlib searchKnn + "
+                       "SW rerank, EF=128 K=128"),
+                   "n_refs": int(len(refs)), "queries_per_gpu": Q, "ef": EF, "k": K,
+                   "parallelism": f"dp{N} (query shards, index replicated per GPU)"},
+    }
+    if not args.full:
+        # the plain run ends here: the headline, with the event times of the timed steps themselves
+        gather = gather_results(D, dev, N * Q, [("sw_ids", d_id), ("sw_scores", d_sc),
+                                               ("search_ids", d_L if flat else d_I), ("search_dists", d_D)])
+        gather_ok = gather_verdict(D, gather)
+        if D.rank == 0:
+            emit({**headline, "index_replication": replication, "gather": gather, "gather_ok": gather_ok,
+                  "breakdown": {"schedule": "sequential: search, then SW rerank, each with the whole chip",
+                                "device_span_ms": round(span_ms, 3), "search_ms": round(search_ms, 3),
+                                "sw_rerank_ms": round(sw_ms, 3), "nhops_mean": round(float(nhops.mean()), 1),
+                                "distances_computed_mean": round(float(ndis.mean()), 1)}})
+        D.close()
+        if gather_ok is False:
+            raise SystemExit(f"rank {D.rank}: the RCCL result gather failed on some rank ({gather})")
+        return
     ndis_computed = ndis
     if not flat:
         # faiss's ndis (the links each hop finds not yet visited: SURVEY.md sec. 8d's algorithmic bytes) from one
@@ -916,8 +1040,6 @@ def main():
     band = sw_band_timing(table, d_I, d_q, d_ql, queries.shape[1], Q, K, args.sw_band, search_ms, sw_ms, ids,
                           d_sc.download(), truth, stream) if (args.sw_band and not flat) else None
 
-    total_reads = float(N * Q * args.steps)
-    value = total_reads / elapsed_max
     gather = gather_results(D, dev, N * Q, [("sw_ids", d_id), ("sw_scores", d_sc), ("search_ids", d_L if flat else d_I),
                                            ("search_dists", d_D)])
     gather_ok = gather_verdict(D, gather)
@@ -927,20 +1049,8 @@ def main():
         if N == 1 and not args.no_cpu:
             cpu = cpu_baseline(refs, fpath if flat else wl["index_path"], queries, q_emb, K, EF, args.cpu_budget, log,
                                flat=flat)
-        workload = wl["desc"] if not flat else (
-                    "C3-flat: the same 1M windows in an hnswlib fp32-L2 index (M=64, EFC=128), hnswlib searchKnn + "
-                    "SW rerank, EF=128 K=128")
         result = {
-            "metric": "mapped reads/sec, 150 bp queries, EF=128 K=128",
-            "value": round(value, 1), "unit": "reads/s", "n_gpus": N, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed_max / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": ("fp32 (L2 distances)" if flat else "fp32 (PQ-ADC distances)") + (
-                " + int32 (SW DP, bit-profile u16 kernel)" if os.environ.get("DRM_SW_BITPROFILE") == "1" else
-                " + u16 integer SW DP (two cells per register)"),
-            "data": f"synthetic (seeded genome/reads, {EMBED_DESC[args.embed]} embeddings; no network)",
-            "config": {"workload": workload, "n_refs": int(len(refs)), "queries_per_gpu": Q, "ef": EF, "k": K,
-                       "parallelism": f"dp{N} (query shards, index replicated per GPU)"},
+            **headline,
             "roofline": {"bound": "hbm", "kernel": search_kernel, "achieved": round(achieved, 2),
                          "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
                          "traffic": traffic, "bytes_per_launch": bytes_launch, "avg_launch_ms": round(search_ms, 4),

@@ -166,7 +166,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void hn
                 if (mn >= dcur)
                     break;
                 dcur = mn;
-                cur = __builtin_amdgcn_readlane(v, __builtin_ctzll(bballot(dk == mn)));
+                // among equally near links (nodes with one PQ code are common) the lowest id, not the lowest slot:
+                // a list's slots are in the order the reverse links' CASes landed, which differs from build to build
+                cur = (int32_t)wave_min_u32(dk == mn ? (uint32_t)v : 0xFFFFFFFFu);
             }
         }
         for (int l = min(ul, a.max_level); l >= 0; --l) {

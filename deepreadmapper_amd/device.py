@@ -82,6 +82,25 @@ class DeviceBuffer:
             check(lib().drm_memcpy_d2h(ptr(out), self.ptr, self.nbytes))
         return out
 
+    def download_rows(self, rows, chunk=1 << 16):
+        """Rows `rows` (ascending indices on the first axis), copied `chunk` rows at a time and only where a wanted
+        row lies, so the host never holds the whole buffer; equals download()[rows]."""
+        rows = np.asarray(rows, dtype=np.int64)
+        out = np.empty((len(rows),) + self.shape[1:], dtype=self.dtype)
+        row_bytes = self.nbytes // self.shape[0] if self.shape[0] else 0
+        buf = np.empty((min(chunk, self.shape[0]),) + self.shape[1:], dtype=self.dtype)
+        i = 0
+        while i < len(rows):
+            lo = int(rows[i]) // chunk * chunk
+            hi = min(lo + chunk, self.shape[0])
+            j = i + int(np.searchsorted(rows[i:], hi))
+            assert 0 <= lo and int(rows[j - 1]) < hi <= self.shape[0], "rows must ascend within the buffer"
+            if row_bytes:
+                check(lib().drm_memcpy_d2h(ptr(buf), self.ptr + lo * row_bytes, (hi - lo) * row_bytes))
+            out[i:j] = buf[rows[i:j] - lo]
+            i = j
+        return out
+
     def zero(self):
         check(lib().drm_memset(self.ptr, 0, max(self.nbytes, 1)))
 

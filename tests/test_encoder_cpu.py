@@ -2,8 +2,9 @@
 tokenizer and GRU model, pinned where the reference offers anything to pin against, and the product's
 IR reader / .drmenc exporter (host-only C-ABI calls, no GPU).
 
-Pins (skipped where /root/reference is absent, i.e. on the GPU box):
-* the tokenizer table against models/tok2index.txt (the reference's vocabulary file);
+Pins (the two that read the model files are skipped where the reference's models/ is absent, i.e. on the GPU box):
+* the tokenizer table against models/tok2index.txt (the reference's vocabulary file, kept as
+  tests/golden/tok2index.txt);
 * the IR's W/R/B layout (z, r, h gates; B = [Wb_z + Rb_z, Wb_r + Rb_r, Wb_h, Rb_h]) against the ONNX
   export shipped beside it, read by a minimal protobuf walk (no onnx/OpenVINO here);
 * the shipped deepreadmapper_amd/models/*.drmenc against the oracle's own IR walk and against a fresh
@@ -24,9 +25,8 @@ SHIPPED = os.path.join(ROOT, "deepreadmapper_amd", "models", "finetuned_sgn33-ne
 need_ref = pytest.mark.skipif(not os.path.exists(IR), reason="reference models/ not present (GPU box)")
 
 
-@need_ref
 def test_tok2index_matches_reference_vocabulary():
-    pairs = dict(l.split(":") for l in open(os.path.join(REF_MODELS, "tok2index.txt")).read().split())
+    pairs = dict(l.split(":") for l in open(os.path.join(ROOT, "tests", "golden", "tok2index.txt")).read().split())
     assert len(pairs) == 96
     for tok, idx in pairs.items():
         assert G._IDX[G.hash_token(*tok.encode())] == int(idx), tok

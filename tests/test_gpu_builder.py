@@ -115,6 +115,21 @@ def test_gpu_build_c3_scale(tmp_path):
     assert rec["gpu"] >= 0.9 * rec["host"]
 
 
+def test_gpu_build_is_reproducible(tmp_path):
+    """Two GPU builds of the same 1M windows write the same file, byte for byte. Every list ends as the set of its
+    closest entries whatever order the reverse links' CASes land in, but its slots are in that order until the final
+    sort, and the greedy descent once broke ties between equally near links by slot (such builds differed in 45 to
+    ~800 neighbour entries); it takes the lowest id now."""
+    from deepreadmapper_amd import synth
+    refs = synth.windows_lookup(synth.genome(500_149, seed=42), 150, 1)
+    files = []
+    for i in range(2):
+        path = str(tmp_path / f"b{i}.index")
+        synth.build_index_gpu_from_rows(refs, path)
+        files.append(open(path, "rb").read())
+    assert len(files[0]) == len(files[1]) and files[0] == files[1]
+
+
 def test_hnswpq_index_cli_builds_c3_on_gpu(tmp_path):
     """The drop-in `hnswpq_index` CLI (src/hnswpq/index.cpp:195-316) builds C3 (a 500,149 bp genome, 1M
     windows) with the GPU builder when a GPU is present (DRM_BUILD_DEVICE=gpu forces it here), writing the

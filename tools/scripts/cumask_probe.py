@@ -26,7 +26,7 @@ ap.add_argument("--queries", type=int, default=1_250_000)
 ap.add_argument("--embed", default="gru")
 ap.add_argument("--fracs", default="0.5,0.375,0.3125,0.25")
 a = ap.parse_args()
-args = argparse.Namespace(cache="/tmp/drm_bench_cache", queries=a.queries, embed=a.embed)
+args = argparse.Namespace(cache=bench.default_cache(), queries=a.queries, embed=a.embed)
 D = bench.Dist()
 wl = bench.prepare_c5(args, D, 0)
 Q, K = wl["Q"], 128

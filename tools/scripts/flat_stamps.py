@@ -11,9 +11,10 @@ from deepreadmapper_amd import synth  # noqa: E402
 from deepreadmapper_amd.device import DeviceBuffer, synchronize  # noqa: E402
 from deepreadmapper_amd.flat import HnswFlatIndex  # noqa: E402
 from deepreadmapper_amd._native import lib, check  # noqa: E402
+import bench  # noqa: E402
 
-w = synth.Workload("c3", 500_149, 100_000, seed=42, read_seed=7).generate("/tmp/drm_bench_cache")
-ix = HnswFlatIndex("/tmp/drm_bench_cache/c3_flat_M64_efc128.hnsw")
+w = synth.Workload("c3", 500_149, 100_000, seed=42, read_seed=7).generate(bench.default_cache())
+ix = HnswFlatIndex(os.path.join(bench.default_cache(), "c3_flat_M64_efc128.hnsw"))
 Q = 100_000
 dq = DeviceBuffer.from_host(w.q_emb[:Q])
 dD, dL = DeviceBuffer((Q, 128), np.float32), DeviceBuffer((Q, 128), np.uint64)

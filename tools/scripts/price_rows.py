@@ -77,7 +77,7 @@ def main():
               f"{' / '.join(f'{waves * l / (r * 1e-9) / 1e9:.1f}G' for l, r in zip((1, 2, 3), row))})", flush=True)
     if a.no_hist:
         return
-    args = argparse.Namespace(cache="/tmp/drm_bench_cache", queries=1_250_000, embed="gru")
+    args = argparse.Namespace(cache=bench.default_cache(), queries=1_250_000, embed="gru")
     wl = bench.prepare_c5(args, bench.Dist(), 0)
     counts, deg0 = level0_counts(wl["index_path"])
     h = np.bincount(counts, minlength=deg0 + 1)

@@ -6,7 +6,7 @@ TAG=${1:-r01}; shift || true
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
-BENCH="python3 bench.py --no-cpu --no-host-path --steps 2 --warmup 1 $*"
+BENCH="python3 bench.py --full --no-cpu --no-host-path --steps 2 --warmup 1 $*"
 rocprofv3 -L > $OUT/counters_list.txt 2>&1 || true
 # workload cache (index build etc.) outside the profiler
 timeout -k 10 600 $BENCH > $OUT/warm.json 2> $OUT/warm.err || { echo "warm-up run failed"; tail -5 $OUT/warm.err; exit 1; }

@@ -17,7 +17,7 @@ ap.add_argument("--k", type=int, default=128)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--embed", default="gru")
 a = ap.parse_args()
-wl = bench.prepare_c5(argparse.Namespace(cache="/tmp/drm_bench_cache", queries=1_250_000, embed=a.embed), bench.Dist(), 0)
+wl = bench.prepare_c5(argparse.Namespace(cache=bench.default_cache(), queries=1_250_000, embed=a.embed), bench.Dist(), 0)
 Q, K = wl["Q"], a.k
 ix = HnswPqIndex(wl["index_path"], 0)
 d_x = DeviceBuffer.from_host(wl["q_emb"])

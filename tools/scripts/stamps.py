@@ -12,16 +12,16 @@ from deepreadmapper_amd import synth  # noqa: E402
 from deepreadmapper_amd.device import DeviceBuffer, synchronize  # noqa: E402
 from deepreadmapper_amd.search import HnswPqIndex  # noqa: E402
 from deepreadmapper_amd._native import lib, check  # noqa: E402
+import bench  # noqa: E402
 
 if len(sys.argv) > 1 and sys.argv[1] in ("c5", "c5gru"):  # the bench's C5 workload (built here if absent)
     import argparse
-    import bench
-    args = argparse.Namespace(cache="/tmp/drm_bench_cache", queries=1_250_000,
+    args = argparse.Namespace(cache=bench.default_cache(), queries=1_250_000,
                               embed="gru" if sys.argv[1] == "c5gru" else "kmer3")
     wl = bench.prepare_c5(args, bench.Dist(), 0)
     q_emb, index_path = wl["q_emb"], wl["index_path"]
 else:
-    w = synth.Workload("c3", 500_149, 100_000, seed=42, read_seed=7).generate("/tmp/drm_bench_cache")
+    w = synth.Workload("c3", 500_149, 100_000, seed=42, read_seed=7).generate(bench.default_cache())
     q_emb, index_path = w.q_emb, w.index_path
 ix = HnswPqIndex(index_path)
 Q = len(q_emb)
