@@ -377,9 +377,11 @@ typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 // ---- integer cells. A score s (0 <= s <= 1023) is the 16-bit pattern s, i.e. the fp16 subnormal s * 2^-24: fp16
 // ordering of non-negative patterns below 0x7C00 is the integer ordering (subnormals included: fp16 denormals are
 // kept, the default FP mode), so v_pk_maximum3_f16 is an exact integer max3. The diagonal term (+2 on a match) is
-// added by v_add_u32 across both halves: the low half stays below 2^16 (s <= 1023 + 2), so no carry crosses. One
-// cell pair costs a 32-bit add (2 cycles per wave64 instruction on gfx950), a packed max3 and a packed saturating
-// subtract (4 each), and half a packed max3 for the best: 12 issue cycles (profiles/r02/valu_rate_probe.txt).
+// added across the halves by an integer add: every half stays below 2^16 (s <= 1023 + 2), so no carry crosses. The
+// add is 64 bits wide (iadd2 below), two columns of both candidates at once; column 1 and a last column without a
+// partner take a v_add_u32. One cell pair costs half a 64-bit add, a packed max3, a packed saturating subtract and
+// half a packed max3 for the best: 3 instructions, each at the packed rate of ~4.5 cycles per wave64 instruction at
+// 2 waves per SIMD (profiles/r07/valu_rate_mix64.txt; 3.5 with a 32-bit add per column before).
 __device__ __forceinline__ uint32_t imax3(uint32_t a, uint32_t b, uint32_t c)
 {
     const h2 r = __builtin_elementwise_maximum(__builtin_elementwise_maximum(__builtin_bit_cast(h2, a), __builtin_bit_cast(h2, b)),
@@ -391,6 +393,14 @@ __device__ __forceinline__ uint32_t idec(uint32_t a) // max(0, s - 1) in both ha
     typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
     return __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(u16x2, a), (u16x2){1, 1}));
 }
+// The diagonal terms of two adjacent columns in one instruction: a 64-bit add over two cell pairs (four 16-bit
+// halves, each <= 1023 + 2, so no carry leaves a half). Written out so that it stays one v_lshl_add_u64.
+__device__ __forceinline__ uint64_t iadd2(uint64_t h, uint64_t w)
+{
+    uint64_t s;
+    asm("v_lshl_add_u64 %0, %1, 0, %2" : "=v"(s) : "v"(h), "v"(w));
+    return s;
+}
 
 // R DP rows in one pass over the LQ columns (rows = consecutive candidate bytes i .. i + R - 1): at step j row r
 // computes column j - r, from the value the row above it wrote there one step earlier, so one wave issues from R
@@ -400,8 +410,11 @@ __device__ __forceinline__ uint32_t idec(uint32_t a) // max(0, s - 1) in both ha
 // of such chains a SIMD holds (one wave per SIMD ran at 46 % of two; the 150-register row
 // leaves room for two waves only), so R is the lever. Per row, the profile words of PF groups of 4 columns are
 // read ahead of the one in use (one ds_read_b128 each), and a group's slot is refilled once the last row is past
-// it. The best takes one max3 per two cells. pp[r]: the pair-profile row of DP row i + r (match terms of the two
-// candidates' bytes against every query column).
+// it. The best takes one max3 per two cells. The diagonal terms are formed two columns at a time: at an odd column c
+// the row adds (H[c], H[c + 1]), both still the row above's, to the profile words of columns c + 1 and c + 2 (the
+// x,y or z,w of one group) in one 64-bit add, uses the low word at the next step and carries the high word (td2) to
+// the step after; so a profile word is read at most one column earlier than its use. pp[r]: the pair-profile row
+// of DP row i + r (match terms of the two candidates' bytes against every query column).
 template <int LQ, int R, int PF>
 __device__ __forceinline__ void sw_rows_i16(uint32_t (&H)[LQ], const uint32_t *const (&pp)[R], uint32_t &best)
 {
@@ -414,7 +427,7 @@ __device__ __forceinline__ void sw_rows_i16(uint32_t (&H)[LQ], const uint32_t *c
             if (g < NG)
                 P[r][g] = *reinterpret_cast<const uint4 *>(pp[r] + 4 * g);
     auto word = [](const uint4 &v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; };
-    uint32_t td[R], left[R];
+    uint32_t td[R], left[R], td2[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         td[r] = P[r][0].x; // column 0: the diagonal is the zero border
@@ -440,7 +453,17 @@ __device__ __forceinline__ void sw_rows_i16(uint32_t (&H)[LQ], const uint32_t *c
             if (c >= 0 && c < LQ) {
                 const uint32_t up = H[c];
                 uint32_t tn = 0u;
-                if (c + 1 < LQ)
+                if ((c & 1) && c + 2 < LQ) {
+                    // columns c + 1, c + 2 at once: (H[c], H[c + 1]) of the row above (row r - 1 wrote H[c + 1]
+                    // earlier in this step, the previous pass for r = 0) plus the x,y or z,w of one profile group
+                    const uint4 &pg = P[r][((c + 1) >> 2) % NS];
+                    const uint64_t s = iadd2((uint64_t)H[c + 1] << 32 | up,
+                                             (uint64_t)word(pg, (c + 2) & 3) << 32 | word(pg, (c + 1) & 3));
+                    tn = (uint32_t)s;
+                    td2[r] = (uint32_t)(s >> 32);
+                } else if (!(c & 1) && c >= 2 && c + 1 < LQ) {
+                    tn = td2[r]; // formed one step ago, together with column c's
+                } else if (c + 1 < LQ) // column 1, and a last column left without a partner
                     tn = up + word(P[r][((c + 1) >> 2) % NS], (c + 1) & 3);
                 const uint32_t v = idec(imax3(td[r], up, left[r]));
                 H[c] = v;

@@ -1,7 +1,8 @@
 // VALU issue-rate probe for gfx950: cycles per wave64 instruction per SIMD for
 // packed fp16 / fp32 ops at 1..8 waves per SIMD, independent and dependent chains; modes 4-6: the SW rerank's
 // cell-pair instruction mix (sw_rerank.hip sw_rows_i16), timed with the shader clock (s_memtime) inside the
-// kernel as well as with events at the nominal clock.
+// kernel as well as with events at the nominal clock; modes 7-8: the 64-bit add (v_lshl_add_u64) alone and in the
+// mix, where it forms the diagonal terms of two columns at once (3 instead of 3.5 instructions per cell pair).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -17,6 +18,8 @@ __global__ __launch_bounds__(64) void probe(float *out, unsigned long long *cyc,
     float f0 = threadIdx.x, f1 = f0 + 1, f2 = f0 + 2, f3 = f0 + 3, f4 = f0 + 4, f5 = f0 + 5, f6 = f0 + 6, f7 = f0 + 7;
     uint32_t x0 = threadIdx.x, x1 = x0 + 1, x2 = x0 + 2, x3 = x0 + 3, x4 = x0 + 4, x5 = x0 + 5, x6 = x0 + 6, x7 = x0 + 7;
     uint32_t t = threadIdx.x & 1 ? 0x20000u : 0x2u, u0 = 3u, u1 = 5u, bst = 0u;
+    uint64_t y0 = threadIdx.x, y1 = y0 + 1, y2 = y0 + 2, y3 = y0 + 3, y4 = y0 + 4, y5 = y0 + 5, y6 = y0 + 6, y7 = y0 + 7;
+    const uint64_t t2 = (uint64_t)t << 32 | t;
     const uint64_t c0 = __builtin_amdgcn_s_memtime();
     for (int i = 0; i < iters; ++i) {
 #pragma unroll
@@ -45,6 +48,20 @@ __global__ __launch_bounds__(64) void probe(float *out, unsigned long long *cyc,
                 MX(x0) MX(x1) MX(x2) MX(x3) MX(x4) MX(x5) MX(x6) MX(x7)
                 SB(x0) SB(x1) SB(x2) SB(x3) SB(x4) SB(x5) SB(x6) SB(x7)
                 BS(x0, x1) BS(x2, x3) BS(x4, x5) BS(x6, x7)
+            } else if (MODE == 7) { // 8 independent v_lshl_add_u64 (shift 0: a plain 64-bit add)
+#define A64(y) asm volatile("v_lshl_add_u64 %0, %0, 0, %1" : "+v"(y) : "v"(t2));
+                A64(y0) A64(y1) A64(y2) A64(y3) A64(y4) A64(y5) A64(y6) A64(y7)
+            } else if (MODE == 8) {
+                // the same 8 cell pairs as MODE 4 with the diag add of two columns in one v_lshl_add_u64 (chains
+                // 2k and 2k + 1 are the halves of y_k): 24 instructions per 8 cell pairs
+#define LO(y) uint32_t y##l = (uint32_t)y, y##h = (uint32_t)(y >> 32);
+#define JOIN(y) y = (uint64_t)y##h << 32 | y##l;
+                A64(y0) A64(y1) A64(y2) A64(y3)
+                LO(y0) LO(y1) LO(y2) LO(y3)
+                MX(y0l) MX(y0h) MX(y1l) MX(y1h) MX(y2l) MX(y2h) MX(y3l) MX(y3h)
+                SB(y0l) SB(y0h) SB(y1l) SB(y1h) SB(y2l) SB(y2h) SB(y3l) SB(y3h)
+                BS(y0l, y0h) BS(y1l, y1h) BS(y2l, y2h) BS(y3l, y3h)
+                JOIN(y0) JOIN(y1) JOIN(y2) JOIN(y3)
             } else { // 8 independent v_add_u32
                 asm volatile("v_add_u32 %0, %0, %1" : "+v"(x0) : "v"(t));
                 asm volatile("v_add_u32 %0, %0, %1" : "+v"(x1) : "v"(t));
@@ -60,7 +77,8 @@ __global__ __launch_bounds__(64) void probe(float *out, unsigned long long *cyc,
     const uint64_t c1 = __builtin_amdgcn_s_memtime();
     h2 s = a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7;
     out[blockIdx.x * 64 + threadIdx.x] = (float)s.x + (float)s.y + f0 + f1 + f2 + f3 + f4 + f5 + f6 + f7 +
-                                         (float)(x0 ^ x1 ^ x2 ^ x3 ^ x4 ^ x5 ^ x6 ^ x7 ^ bst);
+                                         (float)(x0 ^ x1 ^ x2 ^ x3 ^ x4 ^ x5 ^ x6 ^ x7 ^ bst) +
+                                         (float)(y0 ^ y1 ^ y2 ^ y3 ^ y4 ^ y5 ^ y6 ^ y7);
     if (threadIdx.x == 0)
         cyc[blockIdx.x] = c1 - c0; // this wave's loop, in shader clocks
 }
@@ -78,9 +96,11 @@ int main(int argc, char **argv)
     unsigned long long *hcyc = (unsigned long long *)std::malloc(sizeof(unsigned long long) * cus * 32);
     const int iters = 16384;
     const char *names[] = {"v_pk_add_f16 indep", "v_pk_maximum3_f16 indep", "v_add_f32 indep", "v_pk_add_f16 dep chain",
-                           "SW mix (v_add_u32)", "SW mix (v_pk_add_u16)", "v_add_u32 indep"};
-    const double per_iter[] = {64, 64, 64, 64, 8 * 28, 8 * 28, 64}; // instructions per loop iteration
-    for (int mode = 0; mode < 7; ++mode)
+                           "SW mix (v_add_u32)", "SW mix (v_pk_add_u16)", "v_add_u32 indep", "v_lshl_add_u64 indep",
+                           "SW mix (v_lshl_add_u64)"};
+    const double per_iter[] = {64, 64, 64, 64, 8 * 28, 8 * 28, 64, 64, 8 * 24}; // instructions per loop iteration
+    const double per_pair[] = {0, 0, 0, 0, 3.5, 3.5, 0, 0, 3.0}; // the mixes: instructions per cell pair
+    for (int mode = 0; mode < 9; ++mode)
         for (int wps = 1; wps <= 8; wps *= 2) {
             const int grid = cus * 4 * wps;
             hipEvent_t e0, e1;
@@ -95,6 +115,8 @@ int main(int argc, char **argv)
                 if (mode == 4) hipLaunchKernelGGL(probe<4>, dim3(grid), dim3(64), 0, 0, out, cyc, iters);
                 if (mode == 5) hipLaunchKernelGGL(probe<5>, dim3(grid), dim3(64), 0, 0, out, cyc, iters);
                 if (mode == 6) hipLaunchKernelGGL(probe<6>, dim3(grid), dim3(64), 0, 0, out, cyc, iters);
+                if (mode == 7) hipLaunchKernelGGL(probe<7>, dim3(grid), dim3(64), 0, 0, out, cyc, iters);
+                if (mode == 8) hipLaunchKernelGGL(probe<8>, dim3(grid), dim3(64), 0, 0, out, cyc, iters);
                 hipEventRecord(e1);
                 hipEventSynchronize(e1);
             }
@@ -111,9 +133,12 @@ int main(int argc, char **argv)
             // the s_memtime figure is one wave's own loop: the SIMD's rate only when its waves run side by side for the
             // whole loop (exact at 1 wave per SIMD; at more, staggered waves make it read low)
             std::printf("%-26s waves/SIMD=%d  %.2f cycles per wave64 instr per SIMD at the nominal clock, %.2f by s_memtime"
-                        " (%.3f ms, clk %d MHz, per-wave %.0f MHz)\n",
+                        " (%.3f ms, clk %d MHz, per-wave %.0f MHz)",
                         names[mode], wps, ev_cyc / (ops_per_wave * wps), wc / (ops_per_wave * wps), ms, clk / 1000,
                         wc / (ms * 1e-3) / 1e6);
+            if (per_pair[mode] > 0) // the whole SIMD's nominal cycles per cell pair, i.e. per per_pair instructions
+                std::printf(", %.2f nominal cycles per cell pair", ev_cyc / (ops_per_wave * wps) * per_pair[mode]);
+            std::printf("\n");
         }
     return 0;
 }
