@@ -44,6 +44,7 @@ EXPORTS = [
     "drm_post_process_l2_dynamic", "drm_post_process_l2_dynamic_device",
     "drm_index_set_search_waves", "drm_search_rerank_device",
     "drm_index_set_exact_stats", "drm_index_broadcast", "drm_index_clone", "drm_device_chase_latency", "drm_device_chase_rows",
+    "drm_sw_align", "drm_sw_align_device", "drm_sam_cigar",
 ]
 
 
@@ -191,6 +192,9 @@ def lib():
         "drm_post_process_l2_dynamic": (C.c_int, [vp, vp, i64, i32, vp, i32, i64, i32, i32, vp, vp, vp,
                                                   C.POINTER(i64)]),
         "drm_post_process_l2_dynamic_device": (C.c_int, [vp, vp, i64, i32, vp, i32, i64, i32, i32, vp, vp, vp, vp]),
+        "drm_sw_align": (C.c_int, [vp, vp, vp, i64, vp, vp, i32, i64, vp, vp, i32]),
+        "drm_sw_align_device": (C.c_int, [vp, vp, vp, i64, vp, vp, i32, i64, vp, vp, i32, vp]),
+        "drm_sam_cigar": (C.c_int, [vp, vp, i32, i32, i32, i32, C.c_uint64, C.POINTER(i64), C.c_char_p, i32]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name, None)

@@ -256,7 +256,7 @@ void free_index(drm::DeviceIndex &d)
 extern "C" {
 
 const char *drm_last_error(void) { return drm::g_last_error.c_str(); }
-int drm_version(void) { return 100; /* 0.1.0 */ }
+int drm_version(void) { return 200; /* 0.2.0 */ }
 
 int drm_device_count(int *n)
 {
@@ -1557,6 +1557,101 @@ int drm_post_process_sw_dynamic(drm_refs *refs, const int64_t *neighbors, int64_
 {
     return post_process_host(true, refs, neighbors, nq, kk, queries, q_len, q_stride, stride, k, k_clusters,
                              top_scores, top_ids, counts, bad_query);
+}
+
+// ------------------------------------------------------------------------------- SW alignment (sw_align.hip)
+static drm::AlignArgs make_align_args(const drm_refs *refs, const uint64_t *ids, const int64_t *pq, int64_t npairs,
+                                      const uint8_t *q, const int32_t *ql, int32_t q_stride, int64_t nq,
+                                      drm_sw_alignment *out, uint32_t *ops, int32_t ops_stride)
+{
+    if (!refs)
+        throw Error(DRM_ERR_ARG, "null refs");
+    if (npairs < 0 || nq < 0 || q_stride < 0 || ops_stride < 0)
+        throw Error(DRM_ERR_ARG, "negative npairs / nq / q_stride / ops_stride");
+    drm::AlignArgs a{};
+    a.refs = refs->dev.windows;
+    a.n_ref = refs->dev.genome ? 0 : refs->dev.n_ref;
+    a.ref_len = refs->dev.ref_len;
+    a.row_stride = refs->dev.row_stride;
+    a.genome = refs->dev.genome;
+    a.glen = refs->dev.glen;
+    a.window_ids = ids;
+    a.pair_query = pq;
+    a.npairs = npairs;
+    a.queries = q;
+    a.q_len = ql;
+    a.q_stride = q_stride;
+    a.nq = nq;
+    a.out = out;
+    a.ops = ops;
+    a.ops_stride = ops_stride;
+    return a;
+}
+
+int drm_sw_align_device(drm_refs *refs, const uint64_t *d_window_ids, const int64_t *d_pair_query, int64_t npairs,
+                        const uint8_t *d_queries, const int32_t *d_q_len, int32_t q_stride, int64_t nq,
+                        drm_sw_alignment *d_out, uint32_t *d_ops, int32_t ops_stride, void *stream)
+{
+    return guarded([&] {
+        drm::AlignArgs a = make_align_args(refs, d_window_ids, d_pair_query, npairs, d_queries, d_q_len, q_stride, nq,
+                                           d_out, d_ops, ops_stride);
+        if (npairs == 0)
+            return;
+        if (!d_window_ids || !d_pair_query || !d_out || (!d_ops && ops_stride > 0) || (nq > 0 && (!d_queries || !d_q_len)))
+            throw Error(DRM_ERR_ARG, "null argument");
+        DRM_HIP_CHECK(hipSetDevice(refs->dev.device));
+        // max query length bounded by the row stride of the query buffer
+        drm::launch_sw_align(refs->dev, a, q_stride, (hipStream_t)stream);
+    });
+}
+
+int drm_sw_align(drm_refs *refs, const uint64_t *window_ids, const int64_t *pair_query, int64_t npairs,
+                 const uint8_t *queries, const int32_t *q_len, int32_t q_stride, int64_t nq, drm_sw_alignment *out,
+                 uint32_t *ops, int32_t ops_stride)
+{
+    return guarded([&] {
+        drm::AlignArgs a = make_align_args(refs, nullptr, nullptr, npairs, nullptr, nullptr, q_stride, nq, nullptr,
+                                           nullptr, ops_stride);
+        if (npairs == 0)
+            return;
+        if (!window_ids || !pair_query || !out || (!ops && ops_stride > 0) || (nq > 0 && (!queries || !q_len)))
+            throw Error(DRM_ERR_ARG, "null argument");
+        int max_q = 0;
+        for (int64_t i = 0; i < nq; ++i) {
+            if (q_len[i] < 0 || q_len[i] > q_stride)
+                throw Error(DRM_ERR_ARG, "query length outside [0, q_stride]");
+            max_q = std::max(max_q, q_len[i]);
+        }
+        for (int64_t p = 0; p < npairs; ++p)
+            if (pair_query[p] < 0 || pair_query[p] >= nq)
+                throw Error(DRM_ERR_ARG, "pair " + std::to_string(p) + " names query " + std::to_string(pair_query[p]) +
+                                             " outside [0, " + std::to_string(nq) + ")");
+        DRM_HIP_CHECK(hipSetDevice(refs->dev.device));
+        DevBuf<uint64_t> di((size_t)npairs);
+        DevBuf<int64_t> dp((size_t)npairs);
+        DevBuf<uint8_t> dq((size_t)nq * (size_t)q_stride);
+        DevBuf<int32_t> dl((size_t)nq);
+        DevBuf<drm_sw_alignment> dout((size_t)npairs);
+        DevBuf<uint32_t> dops((size_t)npairs * (size_t)ops_stride);
+        di.upload(window_ids);
+        dp.upload(pair_query);
+        if (dq.n)
+            dq.upload(queries);
+        dl.upload(q_len);
+        if (dops.n) // words past a pair's n_ops read as 0
+            DRM_HIP_CHECK(hipMemset(dops.p, 0, sizeof(uint32_t) * dops.n));
+        a.window_ids = di.p;
+        a.pair_query = dp.p;
+        a.queries = dq.p;
+        a.q_len = dl.p;
+        a.out = dout.p;
+        a.ops = dops.p;
+        drm::launch_sw_align(refs->dev, a, max_q, nullptr);
+        DRM_HIP_CHECK(hipDeviceSynchronize());
+        dout.download(out);
+        if (dops.n)
+            dops.download(ops);
+    });
 }
 
 // ------------------------------------------------------------------------------- L2 rerank

@@ -270,6 +270,28 @@ void launch_sw_pairs(const uint8_t *d_s1, const int64_t *d_off1, const int32_t *
                      const int64_t *d_off2, const int32_t *d_len2, int64_t npairs, int32_t *d_scores, int max_len2,
                      hipStream_t stream);
 
+// SW alignment with traceback (sw_align.hip): one wave per (window id, query) pair
+struct AlignArgs {
+    const uint8_t *refs; // static table (null for a genome handle)
+    int64_t n_ref;
+    int32_t ref_len;
+    int64_t row_stride;
+    const uint8_t *genome; // genome handle: window id w = genome[w / 2 ..+ ref_len), reverse-complemented for odd w
+    int64_t glen;
+    const uint64_t *window_ids; // [npairs]
+    const int64_t *pair_query;  // [npairs] index into queries
+    int64_t npairs;
+    const uint8_t *queries; // [nq][q_stride]
+    const int32_t *q_len;
+    int32_t q_stride;
+    int64_t nq;
+    drm_sw_alignment *out; // [npairs]
+    uint32_t *ops;         // [npairs][ops_stride] BAM words, forward order
+    int32_t ops_stride;
+};
+constexpr int kAlignMaxLen = 256; // longest query and window of the alignment kernel
+void launch_sw_align(const DeviceRefs &refs, AlignArgs a, int max_qlen, hipStream_t stream);
+
 // L2 rerank (post_process_l2_static -> batch_reranker, src/utils/post_processor.cpp:1023-1162,
 // src/utils/reranker.cpp:98-195): distances from the window embedding table, libstdc++ partial_sort
 struct L2Args {

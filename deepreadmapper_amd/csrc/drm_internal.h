@@ -139,9 +139,21 @@ std::string extract_fasta_sequence(const std::string &path);
 // write_sam / write_sam_streaming (utils.cpp:336-503) for one block of queries: the SAM lines of
 // queries [q0, q0 + nq) whose ids[i][0 .. counts[i]) are dense window ids (ids[i] at ids + i * k).
 // `header` writes @HD / @SQ first (SN ref_name, LN ref_len: the reference's quirk) and truncates.
+// `aln` (the DRM_SAM_CIGAR mode, no reference counterpart: the reference's CIGAR is a TODO) gives the block's
+// rows their GPU alignment (drm_sw_align of window ids[i * k + j] with the tagged query q0 + i): row i * k + j has
+// record rec[i * k + j] and its complete operations at ops + ops_off[i * k + j]. The line is then
+//   QNAME FLAG ref POS 60 CIGAR * 0 0 SEQ * AS:i:<score> NM:i:<nm>
+// with the real leftmost POS, soft clips, and SEQ reverse-complemented under flag 16; a status-1 record is
+// written unmapped (FLAG | 4, POS 0, CIGAR *, no tags). Null: the reference's pseudo fields.
+struct SamAlignments {
+    const drm_sw_alignment *rec;
+    const uint32_t *ops;
+    const int64_t *ops_off;
+};
 void write_sam_block(const std::string &path, bool header, const std::string &ref_name, size_t ref_len,
                      const std::vector<std::string> &query_seqs, const std::vector<std::string> &query_ids,
-                     size_t q0, size_t nq, const uint64_t *ids, const int32_t *counts, size_t k);
+                     size_t q0, size_t nq, const uint64_t *ids, const int32_t *counts, size_t k,
+                     const SamAlignments *aln = nullptr);
 
 void build_hnswpq(const float *x, int64_t n, int d, int M_pq, int nbits, int M_hnsw, int efc, double sample_rate,
                   int nthreads, uint64_t seed, const std::string &path);

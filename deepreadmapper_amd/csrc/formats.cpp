@@ -330,10 +330,105 @@ std::string drm::extract_fasta_sequence(const std::string &path)
     return g;
 }
 
+// ----------------------------------------------------------------------- SAM from a GPU alignment
+// CIGAR + POS of one drm_sw_alignment record (include/drm_hip.h: drm_sam_cigar)
+static void sam_cigar(const drm_sw_alignment &a, const uint32_t *ops, int32_t q_len, int32_t tag_prefix,
+                      int32_t tag_postfix, int32_t ref_len, uint64_t window_id, int64_t &pos1, std::string &cigar)
+{
+    using drm::Error;
+    if (a.status != 0)
+        throw Error(DRM_ERR_ARG, a.status == 1 ? "the record holds no alignment (status 1)"
+                                               : "the record's operations are truncated (status 2): align the pair again "
+                                                 "with a larger ops_stride");
+    if (a.n_ops < 0 || (a.n_ops > 0 && !ops))
+        throw Error(DRM_ERR_ARG, "null operations");
+    const int32_t lead = a.q_begin - tag_prefix, trail = (q_len - tag_postfix) - a.q_end;
+    if (tag_prefix < 0 || tag_postfix < 0 || lead < 0 || trail < 0)
+        throw Error(DRM_ERR_ARG, "the alignment reaches into the query's tags");
+    const bool rev = (window_id & 1u) != 0;
+    static const char kOp[] = "MID";
+    cigar.clear();
+    auto clip = [&](int32_t n) {
+        if (n > 0)
+            cigar += std::to_string(n) + "S";
+    };
+    clip(rev ? trail : lead);
+    for (int32_t x = 0; x < a.n_ops; ++x) {
+        const uint32_t w = ops[rev ? a.n_ops - 1 - x : x];
+        if ((w & 15u) > 2u)
+            throw Error(DRM_ERR_ARG, "operation word " + std::to_string(x) + " is not M, I or D");
+        cigar += std::to_string(w >> 4);
+        cigar += kOp[w & 15u];
+    }
+    clip(rev ? lead : trail);
+    pos1 = (int64_t)(window_id / 2) + (rev ? ref_len - a.ref_end : a.ref_begin) + 1;
+}
+
+extern "C" int drm_sam_cigar(const drm_sw_alignment *a, const uint32_t *ops, int32_t q_len, int32_t tag_prefix,
+                             int32_t tag_postfix, int32_t ref_len, uint64_t window_id, int64_t *pos1, char *cigar,
+                             int32_t cigar_cap)
+{
+    try {
+        if (!a || !pos1 || !cigar)
+            throw drm::Error(DRM_ERR_ARG, "null argument");
+        std::string c;
+        int64_t p = 0;
+        sam_cigar(*a, ops, q_len, tag_prefix, tag_postfix, ref_len, window_id, p, c);
+        if ((int64_t)c.size() + 1 > (int64_t)cigar_cap)
+            throw drm::Error(DRM_ERR_ARG, "cigar_cap " + std::to_string(cigar_cap) + " is too small for " +
+                                              std::to_string(c.size() + 1) + " bytes");
+        std::memcpy(cigar, c.c_str(), c.size() + 1);
+        *pos1 = p;
+        return DRM_OK;
+    } catch (const drm::Error &e) {
+        drm::set_last_error(e.what());
+        return e.code;
+    } catch (const std::exception &e) {
+        drm::set_last_error(e.what());
+        return DRM_ERR_ARG;
+    }
+}
+
+// one row of the DRM_SAM_CIGAR mode: real POS / CIGAR, SEQ on the forward strand, AS and NM; a hit without an
+// alignment is written as unmapped
+static void append_aligned_row(std::string &buf, const std::string &qname, int flag, const std::string &ref_name,
+                               size_t ref_len, const std::string &tagged, uint64_t sid,
+                               const drm::SamAlignments &aln, size_t row)
+{
+    const drm_sw_alignment &a = aln.rec[row];
+    // the read is the query without format_fastq's tags (an untagged .txt query is the read itself)
+    const int pre = !tagged.empty() && tagged.front() == '<', post = tagged.size() > 1 && tagged.back() == '>';
+    const std::string clean = tagged.substr((size_t)pre, tagged.size() - (size_t)pre - (size_t)post);
+    std::string cigar = "*";
+    int64_t pos1 = 0;
+    if (a.status == 1)
+        flag |= 4;
+    else
+        sam_cigar(a, aln.ops + aln.ops_off[row], (int32_t)tagged.size(), pre, post, (int32_t)ref_len, sid, pos1, cigar);
+    buf += qname;
+    buf += '\t';
+    buf += std::to_string(flag);
+    buf += '\t';
+    buf += ref_name;
+    buf += '\t';
+    buf += std::to_string(pos1);
+    buf += "\t60\t";
+    buf += cigar;
+    buf += "\t*\t0\t0\t";
+    buf += clean.empty() ? std::string("*") : (flag & 16) ? drm::reverse_complement(clean) : clean;
+    buf += "\t*";
+    if (a.status != 1) {
+        buf += "\tAS:i:" + std::to_string(a.score);
+        buf += "\tNM:i:" + std::to_string(a.nm);
+    }
+    buf += '\n';
+}
+
 // ----------------------------------------------------------------------- SAM (write_sam)
 void drm::write_sam_block(const std::string &path, bool header, const std::string &ref_name, size_t ref_len,
                           const std::vector<std::string> &query_seqs, const std::vector<std::string> &query_ids,
-                          size_t q0, size_t nq, const uint64_t *ids, const int32_t *counts, size_t k)
+                          size_t q0, size_t nq, const uint64_t *ids, const int32_t *counts, size_t k,
+                          const SamAlignments *aln)
 {
     std::ofstream out(path, header ? std::ios::out : std::ios::app);
     if (!out.is_open())
@@ -356,6 +451,10 @@ void drm::write_sam_block(const std::string &path, bool header, const std::strin
             int flag = j == 0 ? 0 : 256; // primary / secondary
             if (sid % 2 == 1)
                 flag |= 16; // reverse complement
+            if (aln) {
+                append_aligned_row(buf, qname, flag, ref_name, ref_len, query_seqs[g], sid, *aln, i * k + (size_t)j);
+                continue;
+            }
             buf += qname;
             buf += '\t';
             buf += std::to_string(flag);

@@ -1,0 +1,204 @@
+// deepreadmapper_amd/csrc/sw_align.hip -- Smith-Waterman alignment with traceback for gfx950.
+//
+// The score kernel (sw_rerank.hip) keeps only the best score. This kernel reruns the full DP of
+// calc_sw_score (src/utils/metrics.cpp:10-45) for the pairs that get printed, records a direction per cell
+// and walks it back: the reference leaves this open ("TODO: Implement real CIGAR - from SW ranker",
+// src/utils/utils.cpp:380-384), so the alignment is the one defined in include/drm_hip.h (drm_sw_align).
+//
+// Mapping: one wave per pair. Lane l owns the C = LQ / 64 query columns
+// [l * C, l * C + C); rows are skewed, at step t lane l works on window row t - l, so a pair takes
+// n + ceil(m / C) - 1 steps. The only value that crosses lanes is the left neighbour's last-column H of the row the lane works
+// on next; it moves one lane up per step in a DPP shift. Directions take 2 bits per cell, one byte per lane
+// and row in LDS ([row][lane], 64 B per row); the traceback runs from LDS in the same kernel.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "drm_device.h"
+
+namespace drm {
+namespace {
+
+// comp_table of the reference (src/utils/parse_inputs.cpp:5-14): A<->T, C<->G, N->N, anything else 0
+__device__ __forceinline__ int comp_byte(int c)
+{
+    return c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'N' ? 'N' : 0;
+}
+
+// lane l receives lane l - 1's value, lane 0 receives 0 (DPP wave_shr:1, no source lane: the old value)
+__device__ __forceinline__ int shift_up1(int x)
+{
+    return __builtin_amdgcn_update_dpp(0, x, 0x138, 0xf, 0xf, false);
+}
+
+// A cell is one signed maximum over its three candidates in the form 4 * H + priority (M 2, D 1, I 0), floored at
+// 3 = "H is 0: the walk stops": the result's upper bits are 4 * H and its low two bits are the direction, with the
+// definition's order of preference (M, then D, then I) settled by the same maximum.
+enum : uint32_t { kDirI = 0, kDirD = 1, kDirM = 2, kDirStop = 3 };
+
+constexpr int kOpsWords = 2 * kAlignMaxLen; // a walk has at most n + m steps, so at most as many runs
+
+// LDS: ops[kOpsWords] u32 | window[256] | dirs[ref_len][64]
+constexpr size_t kAlignLdsFixed = sizeof(uint32_t) * kOpsWords + kAlignMaxLen;
+
+template <int LQ>
+__global__ __launch_bounds__(64) void sw_align_kernel(AlignArgs a)
+{
+    constexpr int C = LQ / 64;
+    static_assert(LQ % 64 == 0 && 2 * C <= 8, "one direction byte per lane and row");
+    extern __shared__ __align__(16) uint8_t smem[];
+    uint32_t *opsbuf = reinterpret_cast<uint32_t *>(smem);
+    uint8_t *wbuf = smem + sizeof(uint32_t) * kOpsWords;
+    uint8_t *dirs = wbuf + kAlignMaxLen;
+    const int lane = threadIdx.x;
+
+    for (int64_t p = blockIdx.x; p < a.npairs; p += gridDim.x) {
+        // ---- the pair's window (CandRow of sw_rerank.hip: table row, genome slice, reverse complement for odd
+        //      ids; an id outside the table / a window past the genome end is the empty string) and query
+        const uint64_t wid = a.window_ids[p];
+        const int64_t qi = a.pair_query[p];
+        const uint8_t *wp = nullptr;
+        int rc = 0;
+        if (a.genome) {
+            const uint64_t pos = wid >> 1;
+            if (pos + (uint64_t)a.ref_len <= (uint64_t)a.glen) {
+                rc = (int)(wid & 1u);
+                wp = a.genome + pos + (rc ? a.ref_len - 1 : 0);
+            }
+        } else if (wid < (uint64_t)a.n_ref) {
+            wp = a.refs + wid * (uint64_t)a.row_stride;
+        }
+        const int n = wp ? a.ref_len : 0;
+        int m = 0;
+        const uint8_t *qp = nullptr;
+        if (qi >= 0 && qi < a.nq) {
+            m = min(max(a.q_len[qi], 0), min(a.q_stride, LQ));
+            qp = a.queries + qi * (int64_t)a.q_stride;
+        }
+        __syncthreads(); // the previous pair's traceback has read its LDS
+        for (int r = lane; r < n; r += 64)
+            wbuf[r] = (uint8_t)(rc ? comp_byte(wp[-r]) : (int)wp[r]);
+        __syncthreads();
+
+        // ---- DP: 4 * H of the lane's C columns for the previous row in registers. -2 pads a column past the query:
+        //      it matches no byte, and such columns lie right of every real one, which never reads them. A padded
+        //      cell is some real cell's H minus its distance from it, so it never reaches the best score either.
+        int qv[C], H4[C];
+        uint32_t cellkey[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const int j0 = lane * C + c;
+            qv[c] = j0 < m ? (int)qp[j0] : -2;
+            H4[c] = 0;
+            cellkey[c] = (uint32_t)(((63 - lane) << 2) | (3 - c)); // larger = further left
+        }
+        int left_cur = 0, left_prev = 0; // 4 * H of the left neighbour's last column: this row, the row above
+        // best cell as one key, H << 17 | (511 - row) << 8 | cellkey: max = (score descending, row ascending,
+        // column ascending)
+        uint32_t best = 0;
+        // the lane of the last real column finishes the last row at step n - 1 + (m - 1) / C
+        const int steps = (n > 0 && m > 0) ? n + (m - 1) / C : 0;
+        for (int t = 0; t < steps; ++t) {
+            const int i0 = t - lane;
+            if (i0 >= 0 && i0 < n) {
+                const int wb = wbuf[i0];
+                int diag = left_prev, left = left_cur;
+                uint32_t dbits = 0, rowbest = 0;
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    const int up = H4[c];
+                    const int km = diag + (wb == qv[c] ? 4 + (int)kDirM : -4 + (int)kDirM);
+                    const int kd = up - 4 + (int)kDirD, ki = left - 4 + (int)kDirI;
+                    const uint32_t k = (uint32_t)max(max(max(km, kd), ki), (int)kDirStop);
+                    dbits |= (k & 3u) << (2 * c);
+                    const uint32_t h4 = k & ~3u;
+                    rowbest = max(rowbest, (h4 << 15) | cellkey[c]);
+                    diag = up;
+                    left = (int)h4;
+                    H4[c] = (int)h4;
+                }
+                best = max(best, rowbest | ((uint32_t)(510 - i0) << 8)); // 511 - (1-based row)
+                dirs[i0 * 64 + lane] = (uint8_t)dbits;
+            }
+            // a lane that has not started yet still holds H = 0: the zero border above row 0
+            left_prev = left_cur;
+            left_cur = shift_up1(H4[C - 1]);
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1)
+            best = max(best, (uint32_t)__shfl_xor((int)best, off));
+        __syncthreads(); // every direction byte is in LDS
+
+        // ---- traceback: every lane walks the same path (LDS broadcasts), so no lane-0 branch surrounds the loop
+        const int score = (int)(best >> 17);
+        const int i_end = score > 0 ? 511 - (int)((best >> 8) & 511u) : 0;
+        const int j_end = score > 0 ? (63 - (int)((best >> 2) & 63u)) * C + (3 - (int)(best & 3u)) + 1 : 0;
+        int i = i_end, j = j_end, nops = 0, n_m = 0, n_gap = 0;
+        uint32_t cur_op = 0, cur_len = 0;
+        while (i > 0 && j > 0) {
+            const int col = j - 1, ln = col / C, c = col - ln * C;
+            const uint32_t d = ((uint32_t)dirs[(i - 1) * 64 + ln] >> (2 * c)) & 3u;
+            if (d == kDirStop)
+                break;
+            const uint32_t op = d == kDirM ? 0u : d == kDirD ? 2u : 1u; // BAM: M 0, I 1, D 2
+            n_m += d == kDirM;
+            n_gap += d != kDirM;
+            if (d != kDirI)
+                --i;
+            if (d != kDirD)
+                --j;
+            if (cur_len > 0 && op != cur_op) {
+                opsbuf[nops++] = (cur_len << 4) | cur_op;
+                cur_len = 0;
+            }
+            cur_op = op;
+            ++cur_len;
+        }
+        if (cur_len > 0)
+            opsbuf[nops++] = (cur_len << 4) | cur_op;
+        __syncthreads();
+        // the walk ran backwards: store the runs reversed
+        const int nstore = min(nops, a.ops_stride);
+        for (int x = lane; x < nstore; x += 64)
+            a.ops[p * (int64_t)a.ops_stride + x] = opsbuf[nops - 1 - x];
+        if (lane == 0) {
+            drm_sw_alignment r;
+            r.score = score;
+            r.ref_begin = i;
+            r.ref_end = i_end;
+            r.q_begin = j;
+            r.q_end = j_end;
+            // score = matches - mismatches - gap bases and n_m = matches + mismatches
+            r.nm = n_gap + (n_m - n_gap - score) / 2;
+            r.n_ops = nops;
+            r.status = score == 0 ? 1 : nops > a.ops_stride ? 2 : 0;
+            a.out[p] = r;
+        }
+    }
+}
+
+} // namespace
+
+void launch_sw_align(const DeviceRefs &refs, AlignArgs a, int max_qlen, hipStream_t stream)
+{
+    if (a.npairs <= 0)
+        return;
+    if (max_qlen > kAlignMaxLen)
+        throw Error(DRM_ERR_UNSUPPORTED,
+                    "query length " + std::to_string(max_qlen) + " > 256 is not supported by the GPU SW alignment kernel");
+    if (refs.ref_len > kAlignMaxLen)
+        throw Error(DRM_ERR_UNSUPPORTED, "window length " + std::to_string(refs.ref_len) +
+                                             " > 256 is not supported by the GPU SW alignment kernel");
+    int cus = 0;
+    DRM_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, refs.device));
+    // bounded grid, each wave loops over pairs: 16 waves per CU (11.6 KB of LDS each at 150-byte windows)
+    const int grid = (int)std::min<int64_t>(a.npairs, (int64_t)std::max(cus, 1) * 16);
+    const size_t lds = kAlignLdsFixed + (size_t)std::max(refs.ref_len, 1) * 64;
+    if (max_qlen <= 192) // 150 bp reads + "<" ">" tags: 3 columns per lane
+        hipLaunchKernelGGL(sw_align_kernel<192>, dim3(grid), dim3(64), lds, stream, a);
+    else
+        hipLaunchKernelGGL(sw_align_kernel<256>, dim3(grid), dim3(64), lds, stream, a);
+    DRM_HIP_CHECK(hipGetLastError());
+}
+
+} // namespace drm

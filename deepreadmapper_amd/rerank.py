@@ -249,6 +249,59 @@ def partial_sort_order(scores, k):
     return [int(i) for i in ids[0]]
 
 
+# ------------------------------------------------------------------------------------------- SW alignment
+# drm_sw_alignment (include/drm_hip.h)
+SW_ALIGNMENT_DTYPE = np.dtype([(f, np.int32) for f in ("score", "ref_begin", "ref_end", "q_begin", "q_end", "nm",
+                                                       "n_ops", "status")])
+
+
+def _sw_align_call(table, wid, pq, qbuf, qlen, ops_stride):
+    rec = np.zeros(len(wid), dtype=SW_ALIGNMENT_DTYPE)
+    ops = np.zeros((len(wid), ops_stride), dtype=np.uint32)
+    check(lib().drm_sw_align(table.handle, ptr(wid), ptr(pq), len(wid), ptr(qbuf), ptr(qlen), qbuf.shape[1],
+                             len(qlen), ptr(rec), ptr(ops) if ops.size else None, int(ops_stride)))
+    return rec, ops
+
+
+def sw_align_arrays(table, window_ids, pair_query, query_seqs, ops_stride=16):
+    """The alignment behind the rerank score (drm_sw_align): pair p aligns window window_ids[p] of a WindowTable
+    or GenomeTable with query pair_query[p] of query_seqs (a list, or pack_queries' (buffer, lengths)). Returns
+    (records, ops): a structured array (SW_ALIGNMENT_DTYPE) and, per pair, its BAM operation words
+    (len << 4 | op, M = 0, I = 1, D = 2) in forward order. Pairs with more than ops_stride runs (status 2) are
+    aligned again as a sub-list with a stride that cannot overflow, so every returned status is 0 or 1."""
+    wid = np.ascontiguousarray(window_ids, dtype=np.uint64)
+    pq = np.ascontiguousarray(pair_query, dtype=np.int64)
+    if wid.shape != pq.shape or wid.ndim != 1:
+        raise ValueError("window_ids and pair_query must be 1-d arrays of one length")
+    qbuf, qlen = query_seqs if isinstance(query_seqs, tuple) else pack_queries(query_seqs)
+    rec, ops = _sw_align_call(table, wid, pq, qbuf, qlen, ops_stride)
+    out = [ops[p, :min(int(rec["n_ops"][p]), ops_stride)].copy() for p in range(len(wid))]
+    again = np.flatnonzero(rec["status"] == 2)
+    if len(again):
+        full = int(qbuf.shape[1]) + int(table.ref_len)
+        rec2, ops2 = _sw_align_call(table, np.ascontiguousarray(wid[again]), np.ascontiguousarray(pq[again]), qbuf,
+                                    qlen, full)
+        for x, p in enumerate(again):
+            rec[p] = rec2[x]
+            out[p] = ops2[x, :int(rec2["n_ops"][x])].copy()
+    return rec, out
+
+
+def sam_cigar(record, ops, q_len, ref_len, window_id, tags=(1, 1)):
+    """(pos1, cigar) of one alignment record (drm_sam_cigar): 1-based leftmost position on the forward strand and
+    the CIGAR with soft clips; both are flipped for an odd window id. `tags` are the bytes to drop from the query's
+    ends (format_fastq's "<" and ">")."""
+    r = np.zeros(1, dtype=SW_ALIGNMENT_DTYPE)
+    r[0] = tuple(int(record[f]) for f in SW_ALIGNMENT_DTYPE.names)
+    o = np.ascontiguousarray(ops, dtype=np.uint32)
+    cap = 16 * (len(o) + 2) + 1
+    buf = C.create_string_buffer(cap)
+    pos = C.c_int64(0)
+    check(lib().drm_sam_cigar(ptr(r), ptr(o) if o.size else None, int(q_len), int(tags[0]), int(tags[1]),
+                              int(ref_len), int(window_id), C.byref(pos), buf, cap))
+    return pos.value, buf.value.decode()
+
+
 # ------------------------------------------------------------------------------------------- L2 rerank
 def embed_windows(table, encoder, stream=None):
     """Fill the table's device embedding of every window with the read encoder (drm_refs_embed): the rows the

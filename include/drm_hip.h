@@ -247,6 +247,48 @@ int drm_post_process_sw_static_device(drm_refs *refs, const int64_t *d_neighbors
                                       int64_t stride, int32_t k, int32_t k_clusters, int32_t *d_top_scores,
                                       uint64_t *d_top_ids, int32_t *d_status, void *stream);
 
+/* ---------------------------------------------------------------- Smith-Waterman alignment (traceback)
+ * The alignment behind a rerank score, for real SAM fields (the reference's open "TODO: Implement real CIGAR -
+ * from SW ranker", src/utils/utils.cpp:380-384, :478-482). The reference has no traceback, so this is the
+ * definition. w = the window bytes of window_ids[p] exactly as the rerank reads them (table row; genome slice,
+ * reverse-complemented for odd ids; empty for an id outside the table or a window past the genome end), rows
+ * i = 1..n; q = the query bytes as passed (tags included), columns j = 1..m; equality is raw byte equality.
+ *   H[i][j] = max(0, H[i-1][j-1] + s, H[i-1][j] - 1, H[i][j-1] - 1), s = +1 on equal bytes, else -1;
+ *   score = max H = calc_sw_score(w, q). End cell: among H == score the smallest i, then the smallest j.
+ *   Traceback from the end cell while H[i][j] > 0, the first true condition deciding the step:
+ *     1. H[i][j] == H[i-1][j-1] + s -> M (both step back)   2. H[i][j] == H[i-1][j] - 1 -> D (a window byte)
+ *     3. otherwise -> I (a query byte).
+ *   ref_begin / q_begin: 0-based, inclusive, where the walk stopped; ref_end / q_end: the end cell's i / j
+ *   (exclusive). nm = mismatching M columns + inserted + deleted bases. Operations in forward order, run-length
+ *   encoded as BAM words (len << 4) | op, M = 0, I = 1, D = 2; no clip operations (they follow from q_begin / q_end).
+ * status: 0 aligned; 1 no alignment (score 0: empty window, id outside the table / genome, pair_query outside
+ * [0, nq) on the device entry point, nothing matches): every other field is 0; 2 aligned but n_ops > ops_stride:
+ * the first ops_stride words are stored and n_ops is the full count (retry those pairs as a sub-list with a larger
+ * stride; ops_stride = q_len + ref_len never overflows). */
+typedef struct {
+    int32_t score, ref_begin, ref_end, q_begin, q_end, nm, n_ops, status;
+} drm_sw_alignment;
+/* Pair p aligns window window_ids[p] with query pair_query[p] (queries [nq x q_stride] bytes, q_len[nq]); out[npairs],
+ * ops [npairs x ops_stride]. Works on a window table and on a genome handle, always with the full DP (the handle's
+ * sw_band is ignored). Queries and windows of up to 256 bytes (DRM_ERR_UNSUPPORTED beyond). Host pointers. */
+int drm_sw_align(drm_refs *refs, const uint64_t *window_ids, const int64_t *pair_query, int64_t npairs,
+                 const uint8_t *queries, const int32_t *q_len, int32_t q_stride, int64_t nq, drm_sw_alignment *out,
+                 uint32_t *ops, int32_t ops_stride);
+/* Device-buffer form, enqueued on `stream`; query lengths are bounded by q_stride (<= 256). */
+int drm_sw_align_device(drm_refs *refs, const uint64_t *d_window_ids, const int64_t *d_pair_query, int64_t npairs,
+                        const uint8_t *d_queries, const int32_t *d_q_len, int32_t q_stride, int64_t nq,
+                        drm_sw_alignment *d_out, uint32_t *d_ops, int32_t ops_stride, void *stream);
+/* Host only: SAM coordinates of one record (status 0, ops[0 .. n_ops) complete). The read is
+ * q[tag_prefix : q_len - tag_postfix]; leading soft clip = q_begin - tag_prefix, trailing soft clip =
+ * (q_len - tag_postfix) - q_end, a zero clip omitted. Even window_id: *pos1 = window_id / 2 + ref_begin + 1 and the
+ * CIGAR is [lead S] ops [trail S]. Odd window_id (the window is the reverse complement of
+ * genome[window_id / 2 ..+ ref_len)): *pos1 = window_id / 2 + (ref_len - ref_end) + 1 and the whole CIGAR is
+ * reversed, clips included, i.e. it describes the reverse-complemented read on the forward strand.
+ * DRM_ERR_ARG: status != 0, an alignment reaching into the tags, or cigar_cap too small for the string + NUL. */
+int drm_sam_cigar(const drm_sw_alignment *a, const uint32_t *ops, int32_t q_len, int32_t tag_prefix,
+                  int32_t tag_postfix, int32_t ref_len, uint64_t window_id, int64_t *pos1, char *cigar,
+                  int32_t cigar_cap);
+
 /* ---------------------------------------------------------------- L2 rerank (the reference's live path)
  * post_process_l2_static (src/utils/post_processor.cpp:1023-1162, called at src/main.cpp:330) ->
  * find_sequences (static) -> Vectorizer::vectorize of the candidate windows -> batch_reranker(k = k_clusters)

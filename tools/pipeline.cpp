@@ -11,7 +11,8 @@
 // use_dynamic cuts the candidate windows from the genome string on the device (post_process_sw_dynamic
 // instead of the static window table); use_streaming writes <output_dir>/results.sam block by block
 // (write_sam_streaming) and, like the reference, skips the .npy outputs -- the reference streams only in
-// its dynamic branch, so static + streaming writes no result file there either.
+// its dynamic branch, so static + streaming writes no result file there either. DRM_SAM_CIGAR=1 replaces the
+// reference's pseudo POS / CIGAR in that SAM by the GPU alignment of every row (drm_sw_align).
 // Sequence inputs are embedded by the reference's GRU model on the GPU (drm_vectorize) when
 // DRM_ENCODER names it (.xml IR or .drmenc) or when the reference's models/ path exists in the working
 // directory (Config::Inference::MODEL_PATH); otherwise by the deterministic 3-mer stand-in. The rerank is
@@ -23,6 +24,7 @@
 #include <cstring>
 #include <filesystem>
 #include <iostream>
+#include <memory>
 #include <numeric>
 #include <thread>
 
@@ -53,6 +55,68 @@ template <class T> struct Pinned {
     ~Pinned() { drm_host_free(p); }
     Pinned(const Pinned &) = delete;
     Pinned &operator=(const Pinned &) = delete;
+};
+
+// DRM_SAM_CIGAR=1: the GPU alignments (drm_sw_align) of one SAM block's rows, ids[i * k + j] for j < cnt[i] against
+// query lo + i. The first pass keeps 16 operation words per row; the rows that need more (status 2) are aligned
+// again as a sub-list with a stride that cannot overflow. Rows past cnt[i] keep an empty record.
+struct BlockAlignments {
+    std::vector<drm_sw_alignment> rec;
+    std::vector<uint32_t> ops;
+    std::vector<int64_t> off;
+    drm::SamAlignments view() const { return {rec.data(), ops.data(), off.data()}; }
+
+    void align(drm_refs *rt, const uint64_t *ids, const int32_t *cnt, size_t m, size_t k, const uint8_t *queries,
+               const int32_t *q_len, int32_t q_stride, int32_t ref_len)
+    {
+        constexpr int32_t kStride = 16;
+        constexpr size_t kChunk = (size_t)1 << 20; // pairs per launch
+        std::vector<uint64_t> wid;
+        std::vector<int64_t> pq, row;
+        for (size_t i = 0; i < m; ++i)
+            for (size_t j = 0; j < k && (int64_t)j < (int64_t)cnt[i]; ++j) {
+                wid.push_back(ids[i * k + j]);
+                pq.push_back((int64_t)i);
+                row.push_back((int64_t)(i * k + j));
+            }
+        const size_t np = wid.size();
+        rec.assign(m * k, drm_sw_alignment{0, 0, 0, 0, 0, 0, 0, 1});
+        off.assign(m * k, 0);
+        std::vector<drm_sw_alignment> r1(np);
+        std::vector<uint32_t> o1(np * kStride);
+        for (size_t c = 0; c < np; c += kChunk) {
+            const size_t nc = std::min(kChunk, np - c);
+            check(drm_sw_align(rt, wid.data() + c, pq.data() + c, (int64_t)nc, queries, q_len, q_stride, (int64_t)m,
+                               r1.data() + c, o1.data() + c * kStride, kStride));
+        }
+        std::vector<uint64_t> wid2;
+        std::vector<int64_t> pq2, idx2;
+        for (size_t p = 0; p < np; ++p)
+            if (r1[p].status == 2) {
+                wid2.push_back(wid[p]);
+                pq2.push_back(pq[p]);
+                idx2.push_back((int64_t)p);
+            }
+        const int32_t full = q_stride + ref_len;
+        std::vector<drm_sw_alignment> r2(wid2.size());
+        std::vector<uint32_t> o2(wid2.size() * (size_t)full);
+        for (size_t c = 0; c < wid2.size(); c += kChunk) {
+            const size_t nc = std::min(kChunk, wid2.size() - c);
+            check(drm_sw_align(rt, wid2.data() + c, pq2.data() + c, (int64_t)nc, queries, q_len, q_stride, (int64_t)m,
+                               r2.data() + c, o2.data() + c * (size_t)full, full));
+        }
+        ops.clear();
+        size_t x2 = 0;
+        for (size_t p = 0; p < np; ++p) {
+            const bool retried = x2 < idx2.size() && idx2[x2] == (int64_t)p;
+            const drm_sw_alignment &r = retried ? r2[x2] : r1[p];
+            const uint32_t *o = retried ? o2.data() + x2 * (size_t)full : o1.data() + p * kStride;
+            x2 += retried;
+            rec[(size_t)row[p]] = r;
+            off[(size_t)row[p]] = (int64_t)ops.size();
+            ops.insert(ops.end(), o, o + r.n_ops);
+        }
+    }
 };
 
 int main(int argc, char *argv[])
@@ -279,6 +343,24 @@ int main(int argc, char *argv[])
         const bool sam_from_search = stream_sam && stride == 1;
         const bool l2_rows = std::getenv("DRM_SAM_L2_ROWS") && std::atoi(std::getenv("DRM_SAM_L2_ROWS")) != 0;
         const bool sam_header_only = stream_sam && stride > 1 && !l2_rows;
+        // DRM_SAM_CIGAR=1: every SAM row gets its real POS / CIGAR / AS / NM from a GPU
+        // alignment of the block's rows (drm_sw_align) before the host thread formats the block. Unset: no
+        // alignment is launched and the file is the reference's.
+        const bool sam_cigar = stream_sam && !sam_header_only && std::getenv("DRM_SAM_CIGAR") &&
+                               std::atoi(std::getenv("DRM_SAM_CIGAR")) != 0;
+        drm_refs *art = rt; // the handle the alignments run on (several devices: one more genome handle on the first)
+        if (sam_cigar && !art)
+            check(drm_refs_create_genome((const uint8_t *)genome.data(), (int64_t)genome.size(), (int32_t)ref_len, device,
+                                         &art));
+        // rows of one alignment pass: DRM_SAM_BLOCK when set, else blocks of about 4M rows
+        auto sam_block = [&](size_t rows_per_query) {
+            size_t block = 1u << 20;
+            if (const char *e = std::getenv("DRM_SAM_BLOCK"))
+                block = std::max<size_t>(1, std::strtoull(e, nullptr, 10));
+            else if (sam_cigar)
+                block = std::max<size_t>(1, std::min<size_t>(block, ((size_t)1 << 22) / std::max<size_t>(rows_per_query, 1)));
+            return block;
+        };
         const bool sam_l2 = stream_sam && stride > 1 && l2_rows && rt && !is_npy && !drm::encoder_model_path().empty();
         if (stream_sam && (size_t)k > (size_t)k_clusters * 2 * stride) // post_processor.cpp:769-772
             throw drm::Error(DRM_ERR_K, "Final k too large. Ensure k < k_clusters * 2 * stride to have enough candidates.");
@@ -339,12 +421,19 @@ int main(int argc, char *argv[])
                 }
                 std::cout << "[MAIN] L2 rerank (dynamic, stride " << stride << ") time: " << ms_since(tl) << " ms"
                           << std::endl;
-                size_t block = 1u << 20;
-                if (const char *e = std::getenv("DRM_SAM_BLOCK"))
-                    block = std::max<size_t>(1, std::strtoull(e, nullptr, 10));
-                for (size_t lo = 0; lo < nq; lo += block) // write_sam_streaming per reranked batch (:1004-1006)
-                    drm::write_sam_block(sam_file, lo == 0, "ref", ref_len, qseqs, qids, lo, std::min(block, nq - lo),
-                                         l2i.data() + lo * k, cnt.data() + lo, (size_t)k);
+                const size_t block = sam_block((size_t)k);
+                for (size_t lo = 0; lo < nq; lo += block) { // write_sam_streaming per reranked batch (:1004-1006)
+                    const size_t m = std::min(block, nq - lo);
+                    BlockAlignments ba;
+                    drm::SamAlignments av{};
+                    if (sam_cigar) {
+                        ba.align(art, l2i.data() + lo * k, cnt.data() + lo, m, (size_t)k, qbuf.p + lo * qs, ql.p + lo,
+                                 (int32_t)qs, (int32_t)ref_len);
+                        av = ba.view();
+                    }
+                    drm::write_sam_block(sam_file, lo == 0, "ref", ref_len, qseqs, qids, lo, m, l2i.data() + lo * k,
+                                         cnt.data() + lo, (size_t)k, sam_cigar ? &av : nullptr);
+                }
             }
         } else if (stream_sam) {
             // post_process_*_dynamic_streaming + write_sam_streaming (src/main.cpp:316-319,
@@ -352,9 +441,7 @@ int main(int argc, char *argv[])
             // GPU works on the next block (blocks of DRM_SAM_BLOCK queries; the file does not depend on it)
             std::cout << "[MAIN] Using STREAMING output to SAM file: " << sam_file << std::endl;
             std::filesystem::create_directories(out_dir);
-            size_t block = 1u << 20;
-            if (const char *e = std::getenv("DRM_SAM_BLOCK"))
-                block = std::max<size_t>(1, std::strtoull(e, nullptr, 10));
+            const size_t block = sam_block(sam_from_search ? (size_t)std::min(k, k_clusters) : (size_t)k);
             std::thread writer;
             std::string werr;
             for (size_t lo = 0; lo < nq && rc == DRM_OK; lo += block) {
@@ -365,23 +452,35 @@ int main(int argc, char *argv[])
                 st.ndis += bs.ndis;
                 st.nhops += bs.nhops;
                 st.kernel_ms += bs.kernel_ms;
+                // the block's rows, and with DRM_SAM_CIGAR their alignments: on the GPU from this thread, while
+                // the writer still formats the previous block
+                const size_t kr = sam_from_search ? (size_t)k_clusters : (size_t)k;
+                const uint64_t *rows = sam_from_search ? reinterpret_cast<const uint64_t *>(I.p) + lo * k_clusters
+                                                       : sw_ids.p + lo * k;
+                auto cnt = std::make_shared<std::vector<int32_t>>(m);
+                auto ba = std::make_shared<BlockAlignments>();
+                if (rc == DRM_OK) {
+                    for (size_t i = 0; i < m; ++i)
+                        (*cnt)[i] = sam_from_search ? std::min(k, k_clusters) : std::max(status.p[lo + i], 0);
+                    if (sam_cigar) {
+                        try {
+                            ba->align(art, rows, cnt->data(), m, kr, qbuf.p + lo * qs, ql.p + lo, (int32_t)qs,
+                                      (int32_t)ref_len);
+                        } catch (...) {
+                            if (writer.joinable())
+                                writer.join();
+                            throw;
+                        }
+                    }
+                }
                 if (writer.joinable())
                     writer.join();
                 if (rc == DRM_OK && werr.empty())
-                    writer = std::thread([&, lo, m] {
+                    writer = std::thread([&, lo, m, kr, rows, cnt, ba] {
                         try {
-                            std::vector<int32_t> cnt(m);
-                            if (sam_from_search) {
-                                std::fill(cnt.begin(), cnt.end(), std::min(k, k_clusters));
-                                drm::write_sam_block(sam_file, lo == 0, "ref", ref_len, qseqs, qids, lo, m,
-                                                     reinterpret_cast<const uint64_t *>(I.p) + lo * k_clusters,
-                                                     cnt.data(), (size_t)k_clusters);
-                                return;
-                            }
-                            for (size_t i = 0; i < m; ++i)
-                                cnt[i] = std::max(status.p[lo + i], 0);
-                            drm::write_sam_block(sam_file, lo == 0, "ref", ref_len, qseqs, qids, lo, m,
-                                                 sw_ids.p + lo * k, cnt.data(), (size_t)k);
+                            const drm::SamAlignments av = ba->view();
+                            drm::write_sam_block(sam_file, lo == 0, "ref", ref_len, qseqs, qids, lo, m, rows,
+                                                 cnt->data(), kr, sam_cigar ? &av : nullptr);
                         } catch (const std::exception &e) {
                             werr = e.what();
                         }
@@ -396,6 +495,8 @@ int main(int argc, char *argv[])
         }
         const std::string err = rc == DRM_OK ? "" : drm_last_error();
         const long search_ms = ms_since(t0);
+        if (art && art != rt)
+            drm_refs_free(art);
         if (rt)
             drm_refs_free(rt);
         if (index)

@@ -1,0 +1,87 @@
+"""SW alignment rate probe (DESIGN.md "SW alignment"): drm_sw_align_device on P pairs of 150-byte windows against
+152-byte tagged reads at 1 % substitutions, each read aligned to the window it was drawn from. HIP events, warm,
+median of --runs runs. For scale it also times the score-only rerank (drm_post_process_sw_static_device) on the same
+pairs (one candidate per read, which leaves most of that kernel's lanes idle) and on as many pairs in the shape it
+is built for (P / 128 reads x 128 candidates). Checks the alignment scores against the rerank's before timing."""
+import argparse
+import statistics
+import sys
+
+import numpy as np
+
+sys.path.insert(0, ".")
+from deepreadmapper_amd import WindowTable, synth  # noqa: E402
+from deepreadmapper_amd._native import check, lib  # noqa: E402
+from deepreadmapper_amd.device import DeviceBuffer, Event, Stream  # noqa: E402
+from deepreadmapper_amd.rerank import SW_ALIGNMENT_DTYPE  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--pairs", type=int, default=65_536)
+ap.add_argument("--runs", type=int, default=7)
+ap.add_argument("--ops-stride", type=int, default=16)
+a = ap.parse_args()
+P, K = a.pairs, 128
+
+g = synth.genome(200_000, seed=3)
+refs = synth.windows_lookup(g, 150, 1)
+table = WindowTable(refs)
+reads, _, truth = synth.simulate_reads(g, P, seed=5)
+q = synth.tag(reads)
+st = Stream()
+d_q = DeviceBuffer.from_host(q)
+d_ql = DeviceBuffer.from_host(np.full(P, q.shape[1], dtype=np.int32))
+d_wid = DeviceBuffer.from_host(truth.astype(np.uint64))
+d_pq = DeviceBuffer.from_host(np.arange(P, dtype=np.int64))
+d_rec = DeviceBuffer(P, SW_ALIGNMENT_DTYPE)
+d_ops = DeviceBuffer((P, a.ops_stride), np.uint32)
+d_nb1 = DeviceBuffer.from_host(truth.reshape(P, 1).astype(np.int64))
+d_sc1, d_id1, d_st1 = DeviceBuffer((P, 1), np.int32), DeviceBuffer((P, 1), np.uint64), DeviceBuffer(P, np.int32)
+nq2 = P // K
+rng = np.random.default_rng(1)
+d_nb2 = DeviceBuffer.from_host(rng.integers(0, len(refs), size=(nq2, K)).astype(np.int64))
+d_sc2, d_id2, d_st2 = DeviceBuffer((nq2, K), np.int32), DeviceBuffer((nq2, K), np.uint64), DeviceBuffer(nq2, np.int32)
+
+
+def align():
+    check(lib().drm_sw_align_device(table.handle, d_wid.ptr, d_pq.ptr, P, d_q.ptr, d_ql.ptr, q.shape[1], P, d_rec.ptr,
+                                    d_ops.ptr, a.ops_stride, st.handle))
+
+
+def rerank_same_pairs():
+    check(lib().drm_post_process_sw_static_device(table.handle, d_nb1.ptr, P, 1, d_q.ptr, d_ql.ptr, q.shape[1], 1, 1, 1,
+                                                  d_sc1.ptr, d_id1.ptr, d_st1.ptr, st.handle))
+
+
+def rerank_native_shape():
+    check(lib().drm_post_process_sw_static_device(table.handle, d_nb2.ptr, nq2, K, d_q.ptr, d_ql.ptr, q.shape[1], 1, K,
+                                                  K, d_sc2.ptr, d_id2.ptr, d_st2.ptr, st.handle))
+
+
+def timed(f):
+    f()  # warm
+    st.synchronize()
+    ts = []
+    for _ in range(a.runs):
+        e0, e1 = Event(), Event()
+        e0.record(st)
+        f()
+        e1.record(st)
+        st.synchronize()
+        ts.append(e0.elapsed_ms(e1))
+    return statistics.median(ts), min(ts), max(ts)
+
+
+align()
+rerank_same_pairs()
+st.synchronize()
+rec = d_rec.download()
+assert np.array_equal(rec["score"], d_sc1.download().reshape(-1)), "alignment score != rerank score"
+assert (rec["status"] == 0).all(), "a read did not align (or needed more than --ops-stride operations)"
+print(f"{P} pairs, 150 B windows x {q.shape[1]} B reads; scores equal the rerank's; mean score "
+      f"{rec['score'].mean():.1f}, mean n_ops {rec['n_ops'].mean():.2f}", flush=True)
+for name, f, n in (("sw_align (DP + traceback)", align, P), ("score-only rerank, same pairs (1 candidate / read)",
+                                                           rerank_same_pairs, P),
+                   (f"score-only rerank, {nq2} reads x {K} candidates", rerank_native_shape, nq2 * K)):
+    med, lo, hi = timed(f)
+    print(f"{name}: median {med:.3f} ms (min {lo:.3f}, max {hi:.3f}, {a.runs} runs) = {n / med / 1e3:.2f} M pairs/s",
+          flush=True)
