@@ -1011,6 +1011,9 @@ int drm_flat_index_load(const char *path, int device, drm_flat_index **out)
             throw Error(DRM_ERR_UNSUPPORTED, "fp32 GPU search needs d % 16 == 0 (hnswlib L2SqrSIMD16Ext)");
         if (h.maxM0 > 4096 || h.maxM > 4096)
             throw Error(DRM_ERR_UNSUPPORTED, "maxM0/maxM > 4096");
+        // the kernel stages an upper-level block (up to maxM links) in the LDS area sized for a level-0 row
+        if (h.maxM > h.maxM0)
+            throw Error(DRM_ERR_UNSUPPORTED, "maxM > maxM0 (hnswlib writes maxM0 = 2 * maxM)");
         if (h.n > 0xFFFFFFFFll)
             throw Error(DRM_ERR_UNSUPPORTED, "more than 2^32 elements");
         DRM_HIP_CHECK(hipSetDevice(device));

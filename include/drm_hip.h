@@ -169,7 +169,8 @@ typedef struct {
 } drm_flat_index_info;
 
 /* new hnswlib::HierarchicalNSW<float>(&space, index_file) (src/hnswlib_dir/test_search.cpp:33):
- * parses and validates an hnswlib saveIndex file, uploads it to `device`. */
+ * parses and validates an hnswlib saveIndex file, uploads it to `device`. DRM_ERR_UNSUPPORTED for a layout
+ * the search kernel has no room for: d % 16 != 0, maxM0 or maxM > 4096, maxM > maxM0, 2^32 elements or more. */
 int drm_flat_index_load(const char *path, int device, drm_flat_index **out);
 int drm_flat_index_free(drm_flat_index *index);
 int drm_flat_index_get_info(const drm_flat_index *index, drm_flat_index_info *info);

@@ -210,7 +210,24 @@ def hnswlib_lib():
         _hl.oracle_hnswlib_search.restype = C.c_int
         _hl.oracle_l2_avx.restype = C.c_float
         _hl.oracle_l2_avx.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        _hl.oracle_hnswlib_maxcand.restype = C.c_size_t
+        _hl.oracle_hnswlib_maxcand.argtypes = []
+        _hl.oracle_hnswlib_tie_queries.restype = None
+        _hl.oracle_hnswlib_tie_queries.argtypes = [C.c_void_p]
     return _hl
+
+
+def hnswlib_maxcand():
+    """Largest candidate_set size any query of the last hnswlib_search call reached (diagnostic)."""
+    return int(hnswlib_lib().oracle_hnswlib_maxcand())
+
+
+def hnswlib_tie_queries():
+    """Queries of the last hnswlib_search call with a tie at an eviction of top_candidates, at a
+    candidate_set pop, and at either (diagnostic): where the heap layouts decide the traversal."""
+    out = np.zeros(3, dtype=np.int64)
+    hnswlib_lib().oracle_hnswlib_tie_queries(out.ctypes.data)
+    return tuple(int(v) for v in out)
 
 
 def l2_avx(x, y):
