@@ -138,9 +138,19 @@ struct FlatBuilder {
         {
             omp_set_lock(&locks[cur]);
             uint32_t *ll = links(cur, level);
-            ll[0] = (uint32_t)sel.size();
-            for (size_t j = 0; j < sel.size(); ++j)
-                ll[1 + j] = sel[j];
+            // hnswlib holds the new element's lock for its whole insertion, so its list is blank here. This builder
+            // does not, and an element inserted by another thread that reached cur through a level above may have
+            // linked itself into this list already; cur can be the only node that points to it. Those links are
+            // kept behind cur's own (overwriting them left nodes no path reaches: 14 to 39 of 1,702 at 4 threads).
+            const uint32_t have = ll[0] & 0xFFFFu;
+            std::vector<uint32_t> early(ll + 1, ll + 1 + have);
+            size_t cnt = 0;
+            for (uint32_t s : sel)
+                ll[1 + cnt++] = s;
+            for (uint32_t e : early)
+                if (cnt < mmax && std::find(sel.begin(), sel.end(), e) == sel.end())
+                    ll[1 + cnt++] = e;
+            ll[0] = (uint32_t)cnt;
             omp_unset_lock(&locks[cur]);
         }
         for (uint32_t s : sel) {

@@ -256,7 +256,7 @@ void free_index(drm::DeviceIndex &d)
 extern "C" {
 
 const char *drm_last_error(void) { return drm::g_last_error.c_str(); }
-int drm_version(void) { return 200; /* 0.2.0 */ }
+int drm_version(void) { return 300; /* 0.3.0 */ }
 
 int drm_device_count(int *n)
 {
@@ -1213,6 +1213,105 @@ int drm_flat_search(drm_flat_index *index, const float *x, int64_t n, int32_t d,
         }
     });
 }
+
+// ------------------------------------------------------------------------ exhaustive scans (exact_scan.hip)
+int drm_exact_search_device(drm_index *index, const float *d_x, int64_t n, int32_t k, float *d_D, int64_t *d_I,
+                            void *stream)
+{
+    return guarded([&] {
+        if (!index)
+            throw Error(DRM_ERR_ARG, "null index");
+        DRM_HIP_CHECK(hipSetDevice(index->dev.device));
+        drm::launch_exact_pq(index->dev, d_x, n, k, d_D, d_I, (hipStream_t)stream, nullptr);
+    });
+}
+
+int drm_exact_search(drm_index *index, const float *x, int64_t n, int32_t d, int32_t k, float *D, int64_t *I,
+                     double *kernel_ms)
+{
+    return guarded([&] {
+        if (n <= 0)
+            throw Error(DRM_ERR_ARG, "Query data is empty");
+        if (!index || !x || !D || !I)
+            throw Error(DRM_ERR_ARG, "null argument");
+        if (d != index->dev.d)
+            throw Error(DRM_ERR_ARG, "query dimension " + std::to_string(d) + " != index dimension " +
+                                         std::to_string(index->dev.d));
+        if (k < 1 || k > drm::kMaxCands)
+            throw Error(DRM_ERR_UNSUPPORTED, "exact search: k must be in [1, 1024], got " + std::to_string(k));
+        DRM_HIP_CHECK(hipSetDevice(index->dev.device));
+        DevBuf<float> dx((size_t)n * d), dD((size_t)n * k);
+        DevBuf<int64_t> dI((size_t)n * k);
+        dx.upload(x);
+        drm::launch_exact_pq(index->dev, dx.p, n, k, dD.p, dI.p, nullptr, kernel_ms);
+        dD.download(D);
+        dI.download(I);
+    });
+}
+
+int drm_exact_search_l2_device(const float *d_base, int64_t n_base, int32_t d, const float *d_x, int64_t n, int32_t k,
+                               float *d_D, int64_t *d_I, void *stream)
+{
+    return guarded([&] {
+        drm::launch_exact_l2(d_base, n_base, d, d_x, n, k, d_D, d_I, nullptr, (hipStream_t)stream, nullptr);
+    });
+}
+
+// the host-pointer fp32 scans: base == nullptr scans d_base (a flat index's vectors) instead of an uploaded matrix
+static void exact_l2_host(const float *base, const float *d_base, const uint64_t *d_labels, int64_t n_base, int32_t d,
+                          const float *x, int64_t n, int32_t k, float *D, void *I, double *kernel_ms)
+{
+    if (n <= 0)
+        throw Error(DRM_ERR_ARG, "Query data is empty");
+    if (!x || !D || !I || (n_base > 0 && !base && !d_base))
+        throw Error(DRM_ERR_ARG, "null argument");
+    if (n_base < 0 || n_base >= (int64_t)1 << 31)
+        throw Error(DRM_ERR_UNSUPPORTED, "exact search: the base must hold fewer than 2^31 rows");
+    if (d <= 0 || d % 16 != 0)
+        throw Error(DRM_ERR_UNSUPPORTED, "exact fp32 search needs d % 16 == 0 (hnswlib L2SqrSIMD16Ext)");
+    if (k < 1 || k > drm::kMaxCands)
+        throw Error(DRM_ERR_UNSUPPORTED, "exact search: k must be in [1, 1024], got " + std::to_string(k));
+    DevBuf<float> db(base ? (size_t)n_base * d : 0), dx((size_t)n * d), dD((size_t)n * k);
+    DevBuf<int64_t> dI((size_t)n * k);
+    if (base && n_base)
+        db.upload(base);
+    dx.upload(x);
+    drm::launch_exact_l2(base ? db.p : d_base, n_base, d, dx.p, n, k, dD.p, dI.p, d_labels, nullptr, kernel_ms);
+    dD.download(D);
+    dI.download(static_cast<int64_t *>(I));
+}
+
+int drm_exact_search_l2(const float *base, int64_t n_base, int32_t d, const float *x, int64_t n, int32_t k, float *D,
+                        int64_t *I, double *kernel_ms)
+{
+    return guarded([&] {
+        if (n > 0 && n_base > 0 && !base)
+            throw Error(DRM_ERR_ARG, "null argument");
+        exact_l2_host(base, nullptr, nullptr, n_base, d, x, n, k, D, I, kernel_ms);
+    });
+}
+
+int drm_flat_exact_search(drm_flat_index *index, const float *x, int64_t n, int32_t d, int32_t k, float *D,
+                          uint64_t *labels, double *kernel_ms)
+{
+    return guarded([&] {
+        if (!index)
+            throw Error(DRM_ERR_ARG, "null argument");
+        if (n > 0 && d != index->dev.d)
+            throw Error(DRM_ERR_ARG, "query dimension " + std::to_string(d) + " != index dimension " +
+                                         std::to_string(index->dev.d));
+        DRM_HIP_CHECK(hipSetDevice(index->dev.device));
+        exact_l2_host(nullptr, index->dev.vec, index->dev.labels, index->dev.ntotal, index->dev.d, x, n, k, D, labels,
+                      kernel_ms);
+    });
+}
+
+int drm_exact_set_slice_rows(int64_t rows)
+{
+    return guarded([&] { (void)drm::exact_set_slice_rows(rows); });
+}
+
+int drm_exact_query_tile(void) { return drm::exact_query_tile(); }
 
 // ------------------------------------------------------------------------------------ SW
 int drm_sw_scores(const uint8_t *s1, const int64_t *off1, const int32_t *len1, const uint8_t *s2,

@@ -210,6 +210,18 @@ void launch_hnsw_flat_search(DeviceFlatIndex &ix, const float *d_x, int64_t n, i
                              uint64_t *d_L, int32_t *d_ndis, int32_t *d_nhops, int32_t *d_nhops_upper,
                              hipStream_t stream);
 
+// ---------------------------------------------------------------------- exhaustive scans (exact_scan.hip)
+// The k smallest (distance, id) over every PQ code of the index / every row of an fp32 matrix,
+// written as drm_search writes; d_labels (fp32, may be null) maps ids on output (padding 2^64-1). Both allocate
+// their workspace, enqueue on `stream`, synchronise it and free the workspace; ms (may be null) receives the device
+// time of the launches. They throw Error for the argument limits of include/drm_hip.h.
+void launch_exact_pq(const DeviceIndex &ix, const float *d_x, int64_t n, int k, float *d_D, int64_t *d_I,
+                     hipStream_t stream, double *ms);
+void launch_exact_l2(const float *d_base, int64_t n_base, int d, const float *d_x, int64_t n, int k, float *d_D,
+                     int64_t *d_I, const uint64_t *d_labels, hipStream_t stream, double *ms);
+int64_t exact_set_slice_rows(int64_t rows); // 0 = default; returns the value kept (rounded up to 64)
+int exact_query_tile();
+
 // ---------------------------------------------------------------------------------- SW rerank
 struct DeviceRefs {
     int device = 0;

@@ -51,6 +51,13 @@ class HnswFlatIndex:
                                            d_nhops_upper.ptr if d_nhops_upper is not None else None,
                                            stream.handle if stream is not None else None))
 
+    def exact_search(self, x, k, with_ms=False):
+        """drm_flat_exact_search: the k nearest of the index's own vectors by exhaustive scan, distances with the
+        bits `search` reports; ties by internal id (file order). Returns D [n,k] f32, labels [n,k] u64 (padding
+        2^64-1) (and the scan's kernel_ms with with_ms)."""
+        from .exact import flat_exact_search
+        return flat_exact_search(self, x, k, with_ms)
+
     def overflows(self):
         c = C.c_int64(0)
         check(lib().drm_flat_search_overflows(self.handle, C.byref(c)))

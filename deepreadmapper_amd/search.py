@@ -79,6 +79,18 @@ class HnswPqIndex:
                                          d_nhops_upper.ptr if d_nhops_upper is not None else None,
                                          stream.handle if stream is not None else None))
 
+    def exact_search(self, x, k, with_ms=False):
+        """drm_exact_search: the k smallest PQ-ADC distances over every code of the index (no graph), with the bits
+        `search` reports for the same id; ties by id, padding (+inf, -1). Returns D, I (and the scan's kernel_ms
+        with with_ms)."""
+        from .exact import pq_exact_search
+        return pq_exact_search(self, x, k, with_ms)
+
+    def exact_search_device(self, d_x, n, k, d_D, d_I, stream=None):
+        """drm_exact_search_device on DeviceBuffers: enqueued on `stream` and synchronised."""
+        from .exact import pq_exact_search_device
+        pq_exact_search_device(self, d_x, n, k, d_D, d_I, stream)
+
     def set_exact_stats(self, on=True):
         """ndis as faiss counts it (links never visited before), from a visited bitmap kept for the count; off
         (the default) the lean kernel reports the distances it computed. Results do not depend on it."""

@@ -192,6 +192,46 @@ int drm_flat_search_overflows(drm_flat_index *index, int64_t *count);
 /* As drm_index_search_errors for the fp32 index (drm_flat_search returns DRM_ERR_INTERNAL on a non-zero count). */
 int drm_flat_search_errors(drm_flat_index *index, int64_t *count);
 
+/* ---------------------------------------------------------------- exhaustive k-NN scans (no graph)
+ * Ground truth for recall figures (no counterpart in the ported back ends; the reference's BruteForce::search,
+ * src/hnswm/bruteforce.cpp:27-86, plays this role in its own): every base row is scored and the k smallest under
+ * the total order (distance, id) are returned, independent of tiling, grid and run.
+ * Limits of all of them: 1 <= k <= 1024 (else DRM_ERR_UNSUPPORTED), n == 0 -> DRM_ERR_ARG "Query data is empty",
+ * fewer than 2^31 base rows. */
+
+/* The PQ-ADC scan over every code of a loaded index: dist(i) is the sequential fp32 sum of the query's distance-table
+ * entries of code i, the same bits drm_search reports for id i. Host pointers: x [n x d] f32; D [n x k] f32 and
+ * I [n x k] int64 filled as drm_search fills them (ascending distance, ties by ascending id, missing slots
+ * (+inf, -1) when k > ntotal). d != the index dimension -> DRM_ERR_ARG. PQ 8 x 8 runs the tiled kernel; any other
+ * shape drm_index_load accepts runs a plain one when its distance table is at most 64 KB (else
+ * DRM_ERR_UNSUPPORTED). kernel_ms (may be NULL) receives the device time of the scan. */
+int drm_exact_search(drm_index *index, const float *x, int64_t n, int32_t d, int32_t k, float *D, int64_t *I,
+                     double *kernel_ms);
+/* The same scan on device-resident buffers: enqueued on `stream` (a hipStream_t, NULL = default) and synchronised
+ * (the workspace for the partial lists is allocated in the call and freed before it returns; the handle keeps no
+ * state of it). */
+int drm_exact_search_device(drm_index *index, const float *d_x, int64_t n, int32_t k, float *d_D, int64_t *d_I,
+                            void *stream);
+/* The fp32 scan over any device-resident row-major matrix d_base [n_base x d] (a flat index's vectors, the table
+ * of drm_refs_embeddings, a builder's input), 16-byte aligned, d % 16 == 0 (else DRM_ERR_UNSUPPORTED): squared L2
+ * in the order of drm_flat_search (hnswlib's L2SqrSIMD16ExtAVX: 8 accumulators over dims i, i + 8, ..., added left
+ * to right; no FMA), the same bits for the same pair. d_D [n x k] f32, d_I [n x k] int64 row numbers, padding
+ * (+inf, -1). Inputs are finite; NaN is not specified. Enqueued on `stream` and synchronised. */
+int drm_exact_search_l2_device(const float *d_base, int64_t n_base, int32_t d, const float *d_x, int64_t n,
+                               int32_t k, float *d_D, int64_t *d_I, void *stream);
+/* The same with host pointers (base and x are uploaded to the current device). */
+int drm_exact_search_l2(const float *base, int64_t n_base, int32_t d, const float *x, int64_t n, int32_t k, float *D,
+                        int64_t *I, double *kernel_ms);
+/* The fp32 scan over a flat index's own vectors: ties by internal id (file order), labels[n x k] receives the
+ * hnswlib label of each internal id (padding 2^64-1, as drm_flat_search). Host pointers. */
+int drm_flat_exact_search(drm_flat_index *index, const float *x, int64_t n, int32_t d, int32_t k, float *D,
+                          uint64_t *labels, double *kernel_ms);
+/* Tuning (process-wide; results do not depend on it): base rows per slice of the scans' grid, rounded up to a
+ * multiple of 64 (and raised where more than 1024 slices would result); 0 = the default split. For the tests. */
+int drm_exact_set_slice_rows(int64_t rows);
+/* Queries per workgroup tile of the PQ 8 x 8 scan (for the tests' batch-edge cases). */
+int drm_exact_query_tile(void);
+
 /* ---------------------------------------------------------------- Smith-Waterman rerank */
 /* Batched calc_sw_score(seq1, seq2) (includes/utils/metrics.hpp:22, src/utils/metrics.cpp:10-45):
  * pair p scores s1[off1[p] .. +len1[p]) against s2[off2[p] .. +len2[p]). Host pointers. */
