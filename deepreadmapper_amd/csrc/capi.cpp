@@ -1707,52 +1707,150 @@ int drm_sw_align_device(drm_refs *refs, const uint64_t *d_window_ids, const int6
     });
 }
 
+// the host-pointer form of both alignment kernels: checks, uploads, `launch(args, longest query)`, downloads
+extern "C++" template <class Launch>
+static void sw_align_host(drm_refs *refs, const uint64_t *window_ids, const int64_t *pair_query, int64_t npairs,
+                          const uint8_t *queries, const int32_t *q_len, int32_t q_stride, int64_t nq,
+                          drm_sw_alignment *out, uint32_t *ops, int32_t ops_stride, Launch &&launch)
+{
+    drm::AlignArgs a = make_align_args(refs, nullptr, nullptr, npairs, nullptr, nullptr, q_stride, nq, nullptr,
+                                       nullptr, ops_stride);
+    if (npairs == 0)
+        return;
+    if (!window_ids || !pair_query || !out || (!ops && ops_stride > 0) || (nq > 0 && (!queries || !q_len)))
+        throw Error(DRM_ERR_ARG, "null argument");
+    int max_q = 0;
+    for (int64_t i = 0; i < nq; ++i) {
+        if (q_len[i] < 0 || q_len[i] > q_stride)
+            throw Error(DRM_ERR_ARG, "query length outside [0, q_stride]");
+        max_q = std::max(max_q, q_len[i]);
+    }
+    for (int64_t p = 0; p < npairs; ++p)
+        if (pair_query[p] < 0 || pair_query[p] >= nq)
+            throw Error(DRM_ERR_ARG, "pair " + std::to_string(p) + " names query " + std::to_string(pair_query[p]) +
+                                         " outside [0, " + std::to_string(nq) + ")");
+    DRM_HIP_CHECK(hipSetDevice(refs->dev.device));
+    DevBuf<uint64_t> di((size_t)npairs);
+    DevBuf<int64_t> dp((size_t)npairs);
+    DevBuf<uint8_t> dq((size_t)nq * (size_t)q_stride);
+    DevBuf<int32_t> dl((size_t)nq);
+    DevBuf<drm_sw_alignment> dout((size_t)npairs);
+    DevBuf<uint32_t> dops((size_t)npairs * (size_t)ops_stride);
+    di.upload(window_ids);
+    dp.upload(pair_query);
+    if (dq.n)
+        dq.upload(queries);
+    dl.upload(q_len);
+    if (dops.n) // words past a pair's n_ops read as 0
+        DRM_HIP_CHECK(hipMemset(dops.p, 0, sizeof(uint32_t) * dops.n));
+    a.window_ids = di.p;
+    a.pair_query = dp.p;
+    a.queries = dq.p;
+    a.q_len = dl.p;
+    a.out = dout.p;
+    a.ops = dops.p;
+    launch(a, max_q);
+    DRM_HIP_CHECK(hipDeviceSynchronize());
+    dout.download(out);
+    if (dops.n)
+        dops.download(ops);
+}
+
 int drm_sw_align(drm_refs *refs, const uint64_t *window_ids, const int64_t *pair_query, int64_t npairs,
                  const uint8_t *queries, const int32_t *q_len, int32_t q_stride, int64_t nq, drm_sw_alignment *out,
                  uint32_t *ops, int32_t ops_stride)
 {
     return guarded([&] {
-        drm::AlignArgs a = make_align_args(refs, nullptr, nullptr, npairs, nullptr, nullptr, q_stride, nq, nullptr,
-                                           nullptr, ops_stride);
+        sw_align_host(refs, window_ids, pair_query, npairs, queries, q_len, q_stride, nq, out, ops, ops_stride,
+                      [&](const drm::AlignArgs &a, int max_q) { drm::launch_sw_align(refs->dev, a, max_q, nullptr); });
+    });
+}
+
+// ---------------------------------------------------------------------- affine-gap alignment (sw_align_affine.hip)
+static drm::AffineAlignArgs make_affine_args(const drm_refs *refs, const drm_sw_scoring *sc, int32_t flank)
+{
+    if (!refs || !sc)
+        throw Error(DRM_ERR_ARG, "null refs / scoring");
+    auto range = [](const char *name, int32_t v, int32_t lo, int32_t hi) {
+        if (v < lo || v > hi)
+            throw Error(DRM_ERR_ARG, std::string("scoring: ") + name + " " + std::to_string(v) + " outside [" +
+                                         std::to_string(lo) + ", " + std::to_string(hi) + "]");
+    };
+    range("match", sc->match, 1, 31);
+    range("mismatch", sc->mismatch, 1, 63);
+    range("gap_open", sc->gap_open, 0, 63);
+    range("gap_extend", sc->gap_extend, 1, 63);
+    if (flank < 0)
+        throw Error(DRM_ERR_ARG, "negative flank");
+    if (flank > 0 && !refs->dev.genome)
+        throw Error(DRM_ERR_ARG, "a flank needs a genome handle: a window table holds nothing beside its rows");
+    if ((int64_t)refs->dev.ref_len + 2 * (int64_t)flank > drm::kAlignMaxLen)
+        throw Error(DRM_ERR_UNSUPPORTED, "window length " + std::to_string(refs->dev.ref_len) + " + 2 * flank " +
+                                             std::to_string(flank) +
+                                             " > 256 is not supported by the GPU affine SW alignment kernel");
+    drm::AffineAlignArgs aa{};
+    aa.match = sc->match;
+    aa.mismatch = sc->mismatch;
+    aa.gap_open = sc->gap_open;
+    aa.gap_extend = sc->gap_extend;
+    aa.flank = flank;
+    return aa;
+}
+
+int drm_sw_align_affine_device(drm_refs *refs, const drm_sw_scoring *scoring, int32_t flank,
+                               const uint64_t *d_window_ids, const int64_t *d_pair_query, int64_t npairs,
+                               const uint8_t *d_queries, const int32_t *d_q_len, int32_t q_stride, int64_t nq,
+                               drm_sw_alignment *d_out, uint32_t *d_ops, int32_t ops_stride, void *stream)
+{
+    return guarded([&] {
+        drm::AffineAlignArgs aa = make_affine_args(refs, scoring, flank);
+        aa.base = make_align_args(refs, d_window_ids, d_pair_query, npairs, d_queries, d_q_len, q_stride, nq, d_out,
+                                  d_ops, ops_stride);
         if (npairs == 0)
             return;
-        if (!window_ids || !pair_query || !out || (!ops && ops_stride > 0) || (nq > 0 && (!queries || !q_len)))
+        if (!d_window_ids || !d_pair_query || !d_out || (!d_ops && ops_stride > 0) || (nq > 0 && (!d_queries || !d_q_len)))
             throw Error(DRM_ERR_ARG, "null argument");
-        int max_q = 0;
-        for (int64_t i = 0; i < nq; ++i) {
-            if (q_len[i] < 0 || q_len[i] > q_stride)
-                throw Error(DRM_ERR_ARG, "query length outside [0, q_stride]");
-            max_q = std::max(max_q, q_len[i]);
-        }
-        for (int64_t p = 0; p < npairs; ++p)
-            if (pair_query[p] < 0 || pair_query[p] >= nq)
-                throw Error(DRM_ERR_ARG, "pair " + std::to_string(p) + " names query " + std::to_string(pair_query[p]) +
-                                             " outside [0, " + std::to_string(nq) + ")");
         DRM_HIP_CHECK(hipSetDevice(refs->dev.device));
-        DevBuf<uint64_t> di((size_t)npairs);
-        DevBuf<int64_t> dp((size_t)npairs);
-        DevBuf<uint8_t> dq((size_t)nq * (size_t)q_stride);
-        DevBuf<int32_t> dl((size_t)nq);
-        DevBuf<drm_sw_alignment> dout((size_t)npairs);
-        DevBuf<uint32_t> dops((size_t)npairs * (size_t)ops_stride);
-        di.upload(window_ids);
-        dp.upload(pair_query);
-        if (dq.n)
-            dq.upload(queries);
-        dl.upload(q_len);
-        if (dops.n) // words past a pair's n_ops read as 0
-            DRM_HIP_CHECK(hipMemset(dops.p, 0, sizeof(uint32_t) * dops.n));
-        a.window_ids = di.p;
-        a.pair_query = dp.p;
-        a.queries = dq.p;
-        a.q_len = dl.p;
-        a.out = dout.p;
-        a.ops = dops.p;
-        drm::launch_sw_align(refs->dev, a, max_q, nullptr);
-        DRM_HIP_CHECK(hipDeviceSynchronize());
-        dout.download(out);
-        if (dops.n)
-            dops.download(ops);
+        drm::launch_sw_align_affine(refs->dev, aa, q_stride, (hipStream_t)stream);
+    });
+}
+
+int drm_sw_align_affine(drm_refs *refs, const drm_sw_scoring *scoring, int32_t flank, const uint64_t *window_ids,
+                        const int64_t *pair_query, int64_t npairs, const uint8_t *queries, const int32_t *q_len,
+                        int32_t q_stride, int64_t nq, drm_sw_alignment *out, uint32_t *ops, int32_t ops_stride)
+{
+    return guarded([&] {
+        drm::AffineAlignArgs aa = make_affine_args(refs, scoring, flank);
+        sw_align_host(refs, window_ids, pair_query, npairs, queries, q_len, q_stride, nq, out, ops, ops_stride,
+                      [&](const drm::AlignArgs &a, int max_q) {
+                          aa.base = a;
+                          drm::launch_sw_align_affine(refs->dev, aa, max_q, nullptr);
+                      });
+    });
+}
+
+int drm_sw_align_region(const drm_refs *refs, uint64_t window_id, int32_t flank, int64_t *start, int32_t *len,
+                        int32_t *reverse)
+{
+    return guarded([&] {
+        if (!refs || !start || !len || !reverse)
+            throw Error(DRM_ERR_ARG, "null argument");
+        if (!refs->dev.genome)
+            throw Error(DRM_ERR_ARG, "drm_sw_align_region needs a genome handle");
+        if (flank < 0)
+            throw Error(DRM_ERR_ARG, "negative flank");
+        if ((int64_t)refs->dev.ref_len + 2 * (int64_t)flank > drm::kAlignMaxLen)
+            throw Error(DRM_ERR_UNSUPPORTED, "window length + 2 * flank > 256");
+        const uint64_t pos = window_id >> 1;
+        *reverse = (int32_t)(window_id & 1u);
+        *start = 0;
+        *len = 0;
+        if (pos + (uint64_t)refs->dev.ref_len > (uint64_t)refs->dev.glen)
+            return;
+        const int64_t s = std::max<int64_t>((int64_t)pos - flank, 0);
+        const int64_t e = std::min<int64_t>((int64_t)pos + refs->dev.ref_len + flank, refs->dev.glen);
+        *start = s;
+        *len = (int32_t)(e - s);
     });
 }
 

@@ -304,6 +304,17 @@ struct AlignArgs {
 constexpr int kAlignMaxLen = 256; // longest query and window of the alignment kernel
 void launch_sw_align(const DeviceRefs &refs, AlignArgs a, int max_qlen, hipStream_t stream);
 
+// Affine-gap alignment over a flanked genome region (sw_align_affine.hip; drm_sw_align_affine):
+// the same pairs and outputs; the region of window id w on a genome handle is genome[max(0, w / 2 - flank),
+// min(glen, w / 2 + ref_len + flank)), at most kAlignMaxLen bytes; flank is 0 on a window table
+struct AffineAlignArgs {
+    AlignArgs base;
+    int32_t match, mismatch, gap_open, gap_extend; // the last three are penalties (drm_sw_scoring)
+    int32_t flank;
+    int32_t dir_lanes; // set by the launch: lanes that hold a query column = direction words per row in LDS
+};
+void launch_sw_align_affine(const DeviceRefs &refs, AffineAlignArgs a, int max_qlen, hipStream_t stream);
+
 // L2 rerank (post_process_l2_static -> batch_reranker, src/utils/post_processor.cpp:1023-1162,
 // src/utils/reranker.cpp:98-195): distances from the window embedding table, libstdc++ partial_sort
 struct L2Args {

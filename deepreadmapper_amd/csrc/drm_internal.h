@@ -145,10 +145,15 @@ std::string extract_fasta_sequence(const std::string &path);
 //   QNAME FLAG ref POS 60 CIGAR * 0 0 SEQ * AS:i:<score> NM:i:<nm>
 // with the real leftmost POS, soft clips, and SEQ reverse-complemented under flag 16; a status-1 record is
 // written unmapped (FLAG | 4, POS 0, CIGAR *, no tags). Null: the reference's pseudo fields.
+// With region_start / region_len set (DRM_SAM_SCORING / DRM_SAM_FLANK: drm_sw_align_affine over the row's flanked
+// region, drm_sw_align_region) the record is relative to genome[region_start[row] ..+ region_len[row]) and the row is
+// formatted by drm_sam_cigar_region's rules; AS is then the affine score.
 struct SamAlignments {
     const drm_sw_alignment *rec;
     const uint32_t *ops;
     const int64_t *ops_off;
+    const int64_t *region_start = nullptr;
+    const int32_t *region_len = nullptr;
 };
 void write_sam_block(const std::string &path, bool header, const std::string &ref_name, size_t ref_len,
                      const std::vector<std::string> &query_seqs, const std::vector<std::string> &query_ids,

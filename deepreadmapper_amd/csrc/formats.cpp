@@ -331,9 +331,11 @@ std::string drm::extract_fasta_sequence(const std::string &path)
 }
 
 // ----------------------------------------------------------------------- SAM from a GPU alignment
-// CIGAR + POS of one drm_sw_alignment record (include/drm_hip.h: drm_sam_cigar)
+// CIGAR + POS of one drm_sw_alignment record over the region genome[region_start ..+ region_len), reverse-complemented
+// when rev (include/drm_hip.h: drm_sam_cigar_region; drm_sam_cigar is the region of a window id)
 static void sam_cigar(const drm_sw_alignment &a, const uint32_t *ops, int32_t q_len, int32_t tag_prefix,
-                      int32_t tag_postfix, int32_t ref_len, uint64_t window_id, int64_t &pos1, std::string &cigar)
+                      int32_t tag_postfix, int64_t region_start, int32_t region_len, bool rev, int64_t &pos1,
+                      std::string &cigar)
 {
     using drm::Error;
     if (a.status != 0)
@@ -345,7 +347,6 @@ static void sam_cigar(const drm_sw_alignment &a, const uint32_t *ops, int32_t q_
     const int32_t lead = a.q_begin - tag_prefix, trail = (q_len - tag_postfix) - a.q_end;
     if (tag_prefix < 0 || tag_postfix < 0 || lead < 0 || trail < 0)
         throw Error(DRM_ERR_ARG, "the alignment reaches into the query's tags");
-    const bool rev = (window_id & 1u) != 0;
     static const char kOp[] = "MID";
     cigar.clear();
     auto clip = [&](int32_t n) {
@@ -361,19 +362,19 @@ static void sam_cigar(const drm_sw_alignment &a, const uint32_t *ops, int32_t q_
         cigar += kOp[w & 15u];
     }
     clip(rev ? lead : trail);
-    pos1 = (int64_t)(window_id / 2) + (rev ? ref_len - a.ref_end : a.ref_begin) + 1;
+    pos1 = region_start + (rev ? region_len - a.ref_end : a.ref_begin) + 1;
 }
 
-extern "C" int drm_sam_cigar(const drm_sw_alignment *a, const uint32_t *ops, int32_t q_len, int32_t tag_prefix,
-                             int32_t tag_postfix, int32_t ref_len, uint64_t window_id, int64_t *pos1, char *cigar,
-                             int32_t cigar_cap)
+extern "C" int drm_sam_cigar_region(const drm_sw_alignment *a, const uint32_t *ops, int32_t q_len, int32_t tag_prefix,
+                                    int32_t tag_postfix, int64_t region_start, int32_t region_len, int32_t reverse,
+                                    int64_t *pos1, char *cigar, int32_t cigar_cap)
 {
     try {
         if (!a || !pos1 || !cigar)
             throw drm::Error(DRM_ERR_ARG, "null argument");
         std::string c;
         int64_t p = 0;
-        sam_cigar(*a, ops, q_len, tag_prefix, tag_postfix, ref_len, window_id, p, c);
+        sam_cigar(*a, ops, q_len, tag_prefix, tag_postfix, region_start, region_len, reverse != 0, p, c);
         if ((int64_t)c.size() + 1 > (int64_t)cigar_cap)
             throw drm::Error(DRM_ERR_ARG, "cigar_cap " + std::to_string(cigar_cap) + " is too small for " +
                                               std::to_string(c.size() + 1) + " bytes");
@@ -387,6 +388,14 @@ extern "C" int drm_sam_cigar(const drm_sw_alignment *a, const uint32_t *ops, int
         drm::set_last_error(e.what());
         return DRM_ERR_ARG;
     }
+}
+
+extern "C" int drm_sam_cigar(const drm_sw_alignment *a, const uint32_t *ops, int32_t q_len, int32_t tag_prefix,
+                             int32_t tag_postfix, int32_t ref_len, uint64_t window_id, int64_t *pos1, char *cigar,
+                             int32_t cigar_cap)
+{
+    return drm_sam_cigar_region(a, ops, q_len, tag_prefix, tag_postfix, (int64_t)(window_id / 2), ref_len,
+                                (int32_t)(window_id & 1u), pos1, cigar, cigar_cap);
 }
 
 // one row of the DRM_SAM_CIGAR mode: real POS / CIGAR, SEQ on the forward strand, AS and NM; a hit without an
@@ -403,8 +412,12 @@ static void append_aligned_row(std::string &buf, const std::string &qname, int f
     int64_t pos1 = 0;
     if (a.status == 1)
         flag |= 4;
+    else if (aln.region_start) // aligned over a flanked region (drm_sw_align_affine)
+        sam_cigar(a, aln.ops + aln.ops_off[row], (int32_t)tagged.size(), pre, post, aln.region_start[row],
+                  aln.region_len[row], (sid & 1u) != 0, pos1, cigar);
     else
-        sam_cigar(a, aln.ops + aln.ops_off[row], (int32_t)tagged.size(), pre, post, (int32_t)ref_len, sid, pos1, cigar);
+        sam_cigar(a, aln.ops + aln.ops_off[row], (int32_t)tagged.size(), pre, post, (int64_t)(sid / 2), (int32_t)ref_len,
+                  (sid & 1u) != 0, pos1, cigar);
     buf += qname;
     buf += '\t';
     buf += std::to_string(flag);

@@ -1,0 +1,254 @@
+// deepreadmapper_amd/csrc/sw_align_affine.hip -- affine-gap Smith-Waterman alignment with traceback over a flanked
+// genome region, for gfx950.
+//
+// The alignment that gets printed (DRM_SAM_CIGAR with DRM_SAM_SCORING / DRM_SAM_FLANK): Gotoh's recurrence with the
+// caller's match / mismatch / gap-open / gap-extend scores over the hit's window widened by `flank` genome bases on
+// either side, as defined in include/drm_hip.h (drm_sw_align_affine). The linear kernel (sw_align.hip) stays the
+// rerank's alignment; at {1, 1, 0, 1} and flank 0 the two definitions coincide.
+//
+// Mapping: that of sw_align.hip -- one wave per pair, lane l owns the C = LQ / 64 query
+// columns [l * C, l * C + C), rows skewed by lane -- with F (the gap that runs down a column) in registers beside H,
+// and E (the gap that runs along a row) carried through the lane's columns and handed to the right neighbour together
+// with H, each in one DPP shift per step. A cell's direction is 4 bits (source of H, "F extended", "E extended"), so a
+// lane writes one 16-bit word per row, [row][lane] over the lanes that hold a query column (102 B per row for 152-byte
+// reads); the traceback runs from LDS in the same kernel.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "drm_device.h"
+
+namespace drm {
+namespace {
+
+// comp_table of the reference (src/utils/parse_inputs.cpp:5-14): A<->T, C<->G, N->N, anything else 0
+__device__ __forceinline__ int comp_byte(int c)
+{
+    return c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'N' ? 'N' : 0;
+}
+
+// lane l receives lane l - 1's value, lane 0 receives `border` (DPP wave_shr:1, no source lane: the old value)
+__device__ __forceinline__ int shift_up1(int border, int x)
+{
+    return __builtin_amdgcn_update_dpp(border, x, 0x138, 0xf, 0xf, false);
+}
+
+// Every value is kept times 4. H is one signed maximum over its candidates in the form 4 * value + priority
+// (M 2, F 1, E 0), floored at 3 = "H is 0: the walk stops", exactly as in sw_align.hip. F and E are a maximum over
+// 4 * (H - open - ext) + 1 and 4 * (F or E - ext): bit 0 of the winner says "the gap was opened here", and an equal
+// pair is won by the opening, which is the definition's "closing wins a tie against extending" seen from the walk.
+enum : uint32_t { kSrcE = 0, kSrcF = 1, kSrcM = 2, kSrcStop = 3, kFExt = 4, kEExt = 8 };
+
+constexpr int kNegInf = -(1 << 20); // the borders' E and F: below every real value, far from overflow, 0 mod 4
+constexpr int kOpsWords = 2 * kAlignMaxLen; // a walk has at most n + m steps, so at most as many runs
+
+// LDS: ops[kOpsWords] u32 | region[256] | query[256] | dirs[n][dir_lanes] u16
+constexpr size_t kAffineLdsFixed = sizeof(uint32_t) * kOpsWords + 2 * kAlignMaxLen;
+
+template <int LQ>
+__global__ __launch_bounds__(64) void sw_align_affine_kernel(AffineAlignArgs aa)
+{
+    constexpr int C = LQ / 64;
+    static_assert(LQ % 64 == 0 && 4 * C <= 16, "one 16-bit direction word per lane and row");
+    const AlignArgs &a = aa.base;
+    extern __shared__ __align__(16) uint8_t smem[];
+    uint32_t *opsbuf = reinterpret_cast<uint32_t *>(smem);
+    uint8_t *wbuf = smem + sizeof(uint32_t) * kOpsWords;
+    uint8_t *qbuf = wbuf + kAlignMaxLen;
+    uint16_t *dirs = reinterpret_cast<uint16_t *>(qbuf + kAlignMaxLen);
+    const int lane = threadIdx.x;
+    const int dir_lanes = aa.dir_lanes; // every query column lies on a lane below it: the launch's ceil(max_qlen / C)
+    const int match4 = 4 * aa.match, mismatch4 = 4 * aa.mismatch, ext4 = 4 * aa.gap_extend;
+    const int open4 = 4 * (aa.gap_open + aa.gap_extend) - 1; // H - open4 = 4 * (H - open - ext) + 1
+
+    for (int64_t p = blockIdx.x; p < a.npairs; p += gridDim.x) {
+        // ---- the pair's region: the table row, or genome[s, e) around the window, reverse-complemented as a whole for
+        //      odd ids; an id outside the table / a window past the genome end is the empty string
+        const uint64_t wid = a.window_ids[p];
+        const int64_t qi = a.pair_query[p];
+        const uint8_t *wp = nullptr;
+        int rc = 0, n = 0;
+        if (a.genome) {
+            const uint64_t pos = wid >> 1;
+            if (pos + (uint64_t)a.ref_len <= (uint64_t)a.glen) {
+                const int64_t s = max((int64_t)pos - aa.flank, (int64_t)0);
+                const int64_t e = min((int64_t)pos + a.ref_len + aa.flank, a.glen);
+                n = min((int)(e - s), kAlignMaxLen);
+                rc = (int)(wid & 1u);
+                wp = a.genome + (rc ? e - 1 : s);
+            }
+        } else if (wid < (uint64_t)a.n_ref) {
+            wp = a.refs + wid * (uint64_t)a.row_stride;
+            n = min(a.ref_len, kAlignMaxLen);
+        }
+        int m = 0;
+        const uint8_t *qp = nullptr;
+        if (qi >= 0 && qi < a.nq) {
+            m = min(max(a.q_len[qi], 0), min(a.q_stride, LQ));
+            qp = a.queries + qi * (int64_t)a.q_stride;
+        }
+        __syncthreads(); // the previous pair's traceback has read its LDS
+        for (int r = lane; r < n; r += 64)
+            wbuf[r] = (uint8_t)(rc ? comp_byte(wp[-r]) : (int)wp[r]);
+
+        // ---- DP: 4 * H and 4 * F of the lane's C columns for the previous row in registers. -2 pads a column past the
+        //      query: it matches no byte, and such columns lie right of every real one, which never reads them. A
+        //      padded cell is some real cell's H minus at least its distance from it, so it never reaches the best score.
+        int qv[C], H4[C], F4[C];
+        uint32_t cellkey[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const int j0 = lane * C + c;
+            qv[c] = j0 < m ? (int)qp[j0] : -2;
+            if (j0 < m)
+                qbuf[j0] = (uint8_t)qv[c];
+            H4[c] = 0;
+            F4[c] = kNegInf;
+            cellkey[c] = (uint32_t)(((63 - lane) << 2) | (3 - c)); // larger = further left
+        }
+        __syncthreads();
+        // the left neighbour's last column: 4 * H of this row and of the row above, 4 * E of this row
+        int left_cur = 0, left_prev = 0, left_e = kNegInf, e_last = kNegInf;
+        // best cell as one key, H << 17 | (511 - row) << 8 | cellkey: max = (score descending, row ascending,
+        // column ascending); H <= 31 * 256 < 2^13
+        uint32_t best = 0;
+        // the lane of the last real column finishes the last row at step n - 1 + (m - 1) / C
+        const int steps = (n > 0 && m > 0) ? n + (m - 1) / C : 0;
+        for (int t = 0; t < steps; ++t) {
+            const int i0 = t - lane;
+            if (i0 >= 0 && i0 < n) {
+                const int wb = wbuf[i0];
+                int diag = left_prev, left = left_cur, e = left_e;
+                uint32_t dbits = 0, rowbest = 0;
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    const int up = H4[c];
+                    const int fk = max(up - open4, F4[c] - ext4);
+                    const int ek = max(left - open4, e - ext4);
+                    const int f = fk & ~1;
+                    e = ek & ~1;
+                    const int km = diag + (wb == qv[c] ? match4 : -mismatch4) + (int)kSrcM;
+                    const uint32_t k = (uint32_t)max(max(max(km, f + (int)kSrcF), e + (int)kSrcE), (int)kSrcStop);
+                    // bit 0 of fk / ek set = opened: "extended" is its complement, at bits 2 and 3
+                    dbits |= ((k & 3u) | ((uint32_t)(~fk & 1) << 2) | ((uint32_t)(~ek & 1) << 3)) << (4 * c);
+                    const uint32_t h4 = k & ~3u;
+                    rowbest = max(rowbest, (h4 << 15) | cellkey[c]);
+                    diag = up;
+                    left = (int)h4;
+                    H4[c] = (int)h4;
+                    F4[c] = f;
+                }
+                e_last = e;
+                best = max(best, rowbest | ((uint32_t)(510 - i0) << 8)); // 511 - (1-based row)
+                if (lane < dir_lanes) // the lanes past it hold padded columns only, which the walk never visits
+                    dirs[i0 * dir_lanes + lane] = (uint16_t)dbits;
+            }
+            // a lane that has not started yet still holds H = 0 and E = -inf: the borders above row 0; lane 0's left
+            // neighbour is column 0, H = 0 and E = -inf on every row
+            left_prev = left_cur;
+            left_cur = shift_up1(0, H4[C - 1]);
+            left_e = shift_up1(kNegInf, e_last);
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1)
+            best = max(best, (uint32_t)__shfl_xor((int)best, off));
+        __syncthreads(); // every direction word is in LDS
+
+        // ---- traceback: every lane walks the same path (LDS broadcasts), so no lane-0 branch surrounds the loop.
+        //      state 0 = H, 1 = F (a run of region bytes, D), 2 = E (a run of query bytes, I)
+        const int score = (int)(best >> 17);
+        const int i_end = score > 0 ? 511 - (int)((best >> 8) & 511u) : 0;
+        const int j_end = score > 0 ? (63 - (int)((best >> 2) & 63u)) * C + (3 - (int)(best & 3u)) + 1 : 0;
+        int i = i_end, j = j_end, nops = 0, nm = 0, state = 0;
+        uint32_t cur_op = 0, cur_len = 0;
+        while (i > 0 && j > 0) {
+            const int col = j - 1, ln = col / C, c = col - ln * C;
+            const uint32_t d = ((uint32_t)dirs[(i - 1) * dir_lanes + ln] >> (4 * c)) & 15u;
+            int move = state; // 1 = D, 2 = I, 3 = M
+            if (state == 0) {
+                const uint32_t src = d & 3u;
+                if (src == kSrcStop)
+                    break;
+                move = src == kSrcM ? 3 : src == kSrcF ? 1 : 2;
+            }
+            uint32_t op; // BAM: M 0, I 1, D 2
+            if (move == 3) {
+                op = 0u;
+                nm += wbuf[i - 1] != qbuf[j - 1];
+                --i;
+                --j;
+                state = 0;
+            } else if (move == 1) {
+                op = 2u;
+                ++nm;
+                state = (d & kFExt) ? 1 : 0;
+                --i;
+            } else {
+                op = 1u;
+                ++nm;
+                state = (d & kEExt) ? 2 : 0;
+                --j;
+            }
+            if (cur_len > 0 && op != cur_op) {
+                opsbuf[nops++] = (cur_len << 4) | cur_op;
+                cur_len = 0;
+            }
+            cur_op = op;
+            ++cur_len;
+        }
+        if (cur_len > 0)
+            opsbuf[nops++] = (cur_len << 4) | cur_op;
+        __syncthreads();
+        // the walk ran backwards: store the runs reversed
+        const int nstore = min(nops, a.ops_stride);
+        for (int x = lane; x < nstore; x += 64)
+            a.ops[p * (int64_t)a.ops_stride + x] = opsbuf[nops - 1 - x];
+        if (lane == 0) {
+            drm_sw_alignment r;
+            r.score = score;
+            r.ref_begin = i;
+            r.ref_end = i_end;
+            r.q_begin = j;
+            r.q_end = j_end;
+            r.nm = nm;
+            r.n_ops = nops;
+            r.status = score == 0 ? 1 : nops > a.ops_stride ? 2 : 0;
+            a.out[p] = r;
+        }
+    }
+}
+
+} // namespace
+
+void launch_sw_align_affine(const DeviceRefs &refs, AffineAlignArgs aa, int max_qlen, hipStream_t stream)
+{
+    if (aa.base.npairs <= 0)
+        return;
+    const int region = refs.ref_len + 2 * aa.flank;
+    if (max_qlen > kAlignMaxLen)
+        throw Error(DRM_ERR_UNSUPPORTED, "query length " + std::to_string(max_qlen) +
+                                             " > 256 is not supported by the GPU affine SW alignment kernel");
+    if (region > kAlignMaxLen)
+        throw Error(DRM_ERR_UNSUPPORTED, "window length " + std::to_string(refs.ref_len) + " + 2 * flank " +
+                                             std::to_string(aa.flank) + " = " + std::to_string(region) +
+                                             " > 256 is not supported by the GPU affine SW alignment kernel");
+    int cus = 0;
+    DRM_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, refs.device));
+    // one direction word per row for each lane that can hold a query column
+    const int cols = max_qlen <= 192 ? 3 : 4; // 150 bp reads + "<" ">" tags: 3 columns per lane
+    aa.dir_lanes = std::max((max_qlen + cols - 1) / cols, 1);
+    // bounded grid, each wave loops over pairs: as many waves per CU as its 160 KB of LDS hold (152-byte reads: 17.4 KB
+    // each at 150-byte windows: 9; 19.0 KB at flank 8: 8; 256 x 256 bytes, 34.5 KB: 4), 16 at the most, rounded down to
+    // a multiple of the CU's 4 SIMDs. The kernel is bound by VALU issue and every wave takes the same number of pairs,
+    // so a SIMD with one wave more than the others sets the time: 9 per CU measured slower than 8.
+    const size_t lds = kAffineLdsFixed + (size_t)std::max(region, 1) * aa.dir_lanes * sizeof(uint16_t);
+    const int per_cu = (int)std::min<size_t>(16, (size_t)160 * 1024 / lds) & ~3; // lds <= 34.5 KB: at least 4
+    const int grid = (int)std::min<int64_t>(aa.base.npairs, (int64_t)std::max(cus, 1) * per_cu);
+    if (cols == 3)
+        hipLaunchKernelGGL(sw_align_affine_kernel<192>, dim3(grid), dim3(64), lds, stream, aa);
+    else
+        hipLaunchKernelGGL(sw_align_affine_kernel<256>, dim3(grid), dim3(64), lds, stream, aa);
+    DRM_HIP_CHECK(hipGetLastError());
+}
+
+} // namespace drm

@@ -263,6 +263,23 @@ def _sw_align_call(table, wid, pq, qbuf, qlen, ops_stride):
     return rec, ops
 
 
+def sw_scoring(scoring):
+    """drm_sw_scoring (match, mismatch, gap_open, gap_extend) as the int32 array the C ABI reads."""
+    s = np.array([int(x) for x in scoring], dtype=np.int32)
+    if s.shape != (4,):
+        raise ValueError("scoring is (match, mismatch, gap_open, gap_extend)")
+    return s
+
+
+def _sw_align_affine_call(table, scoring, flank, wid, pq, qbuf, qlen, ops_stride):
+    rec = np.zeros(len(wid), dtype=SW_ALIGNMENT_DTYPE)
+    ops = np.zeros((len(wid), ops_stride), dtype=np.uint32)
+    check(lib().drm_sw_align_affine(table.handle, ptr(scoring), int(flank), ptr(wid), ptr(pq), len(wid), ptr(qbuf),
+                                    ptr(qlen), qbuf.shape[1], len(qlen), ptr(rec), ptr(ops) if ops.size else None,
+                                    int(ops_stride)))
+    return rec, ops
+
+
 def sw_align_arrays(table, window_ids, pair_query, query_seqs, ops_stride=16):
     """The alignment behind the rerank score (drm_sw_align): pair p aligns window window_ids[p] of a WindowTable
     or GenomeTable with query pair_query[p] of query_seqs (a list, or pack_queries' (buffer, lengths)). Returns
@@ -274,32 +291,76 @@ def sw_align_arrays(table, window_ids, pair_query, query_seqs, ops_stride=16):
     if wid.shape != pq.shape or wid.ndim != 1:
         raise ValueError("window_ids and pair_query must be 1-d arrays of one length")
     qbuf, qlen = query_seqs if isinstance(query_seqs, tuple) else pack_queries(query_seqs)
-    rec, ops = _sw_align_call(table, wid, pq, qbuf, qlen, ops_stride)
+    def call(w, q, stride):
+        return _sw_align_call(table, w, q, qbuf, qlen, stride)
+    rec, ops = call(wid, pq, ops_stride)
+    return _retry_truncated(call, wid, pq, rec, ops, ops_stride, int(qbuf.shape[1]) + int(table.ref_len))
+
+
+def _retry_truncated(call, wid, pq, rec, ops, ops_stride, full):
+    """Per-pair operation lists of one alignment call; the pairs with more than ops_stride runs (status 2) are
+    aligned again as a sub-list with the stride `full`, which cannot overflow."""
     out = [ops[p, :min(int(rec["n_ops"][p]), ops_stride)].copy() for p in range(len(wid))]
     again = np.flatnonzero(rec["status"] == 2)
     if len(again):
-        full = int(qbuf.shape[1]) + int(table.ref_len)
-        rec2, ops2 = _sw_align_call(table, np.ascontiguousarray(wid[again]), np.ascontiguousarray(pq[again]), qbuf,
-                                    qlen, full)
+        rec2, ops2 = call(np.ascontiguousarray(wid[again]), np.ascontiguousarray(pq[again]), full)
         for x, p in enumerate(again):
             rec[p] = rec2[x]
             out[p] = ops2[x, :int(rec2["n_ops"][x])].copy()
     return rec, out
 
 
-def sam_cigar(record, ops, q_len, ref_len, window_id, tags=(1, 1)):
-    """(pos1, cigar) of one alignment record (drm_sam_cigar): 1-based leftmost position on the forward strand and
-    the CIGAR with soft clips; both are flipped for an odd window id. `tags` are the bytes to drop from the query's
-    ends (format_fastq's "<" and ">")."""
+def sw_align_affine_arrays(table, window_ids, pair_query, query_seqs, scoring, flank=0, ops_stride=16):
+    """The affine-gap alignment over a flanked region (drm_sw_align_affine): sw_align_arrays with a scoring
+    (match, mismatch, gap_open, gap_extend), the last three penalties, and on a GenomeTable `flank` genome bases on
+    either side of the window as the target (sw_align_region gives a pair's region; ref_begin / ref_end are relative
+    to it). Pairs with more than ops_stride runs are aligned again, so every returned status is 0 or 1."""
+    wid = np.ascontiguousarray(window_ids, dtype=np.uint64)
+    pq = np.ascontiguousarray(pair_query, dtype=np.int64)
+    if wid.shape != pq.shape or wid.ndim != 1:
+        raise ValueError("window_ids and pair_query must be 1-d arrays of one length")
+    qbuf, qlen = query_seqs if isinstance(query_seqs, tuple) else pack_queries(query_seqs)
+    sc = sw_scoring(scoring)
+
+    def call(w, q, stride):
+        return _sw_align_affine_call(table, sc, flank, w, q, qbuf, qlen, stride)
+    rec, ops = call(wid, pq, ops_stride)
+    return _retry_truncated(call, wid, pq, rec, ops, ops_stride, int(qbuf.shape[1]) + int(table.ref_len) + 2 * int(flank))
+
+
+def sw_align_region(table, window_id, flank):
+    """(start, length, reverse) of a window id's target region on a GenomeTable (drm_sw_align_region): the bytes
+    genome[start : start + length], reverse-complemented when reverse; length 0 for a window past the genome end."""
+    start, n, rev = C.c_int64(0), C.c_int32(0), C.c_int32(0)
+    check(lib().drm_sw_align_region(table.handle, int(window_id), int(flank), C.byref(start), C.byref(n), C.byref(rev)))
+    return start.value, n.value, rev.value
+
+
+def _sam_cigar_call(fn, record, ops, *args):
     r = np.zeros(1, dtype=SW_ALIGNMENT_DTYPE)
     r[0] = tuple(int(record[f]) for f in SW_ALIGNMENT_DTYPE.names)
     o = np.ascontiguousarray(ops, dtype=np.uint32)
     cap = 16 * (len(o) + 2) + 1
     buf = C.create_string_buffer(cap)
     pos = C.c_int64(0)
-    check(lib().drm_sam_cigar(ptr(r), ptr(o) if o.size else None, int(q_len), int(tags[0]), int(tags[1]),
-                              int(ref_len), int(window_id), C.byref(pos), buf, cap))
+    check(fn(ptr(r), ptr(o) if o.size else None, *args, C.byref(pos), buf, cap))
     return pos.value, buf.value.decode()
+
+
+def sam_cigar_region(record, ops, q_len, region_start, region_len, reverse, tags=(1, 1)):
+    """(pos1, cigar) of one record relative to the region genome[region_start ..+ region_len)
+    (drm_sam_cigar_region): sam_cigar's rules, pos1 = region_start + (region_len - ref_end if reverse else
+    ref_begin) + 1, the CIGAR reversed when reverse."""
+    return _sam_cigar_call(lib().drm_sam_cigar_region, record, ops, int(q_len), int(tags[0]), int(tags[1]),
+                           int(region_start), int(region_len), int(bool(reverse)))
+
+
+def sam_cigar(record, ops, q_len, ref_len, window_id, tags=(1, 1)):
+    """(pos1, cigar) of one alignment record (drm_sam_cigar): 1-based leftmost position on the forward strand and
+    the CIGAR with soft clips; both are flipped for an odd window id. `tags` are the bytes to drop from the query's
+    ends (format_fastq's "<" and ">")."""
+    return _sam_cigar_call(lib().drm_sam_cigar, record, ops, int(q_len), int(tags[0]), int(tags[1]), int(ref_len),
+                           int(window_id))
 
 
 # ------------------------------------------------------------------------------------------- L2 rerank

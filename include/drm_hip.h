@@ -330,6 +330,60 @@ int drm_sam_cigar(const drm_sw_alignment *a, const uint32_t *ops, int32_t q_len,
                   int32_t tag_postfix, int32_t ref_len, uint64_t window_id, int64_t *pos1, char *cigar,
                   int32_t cigar_cap);
 
+/* ---------------------------------------------------------------- Affine-gap alignment over a flanked region
+ * A second definition beside drm_sw_align's, for the alignment that gets printed: gaps priced by open + extend, and on
+ * a genome handle a target that reaches `flank` bases past either end of the window, so that neither the window grid
+ * nor an indel clips the read. drm_sw_align and the rerank are untouched by it.
+ * Scoring: mismatch, gap_open and gap_extend are penalties (positive numbers that get subtracted); a gap of L bases
+ * costs gap_open + L * gap_extend. Accepted: match 1..31, mismatch 1..63, gap_open 0..63, gap_extend 1..63
+ * (DRM_ERR_ARG otherwise); with a region of at most 256 rows every score fits the kernel's packed keys.
+ * Target region of window id w, pos = w / 2, on a genome handle with flank >= 0 (DRM_ERR_ARG when negative):
+ *   pos + ref_len > glen: empty (status 1), as the window is for drm_sw_align; otherwise genome[s, e) with
+ *   s = max(0, pos - flank), e = min(glen, pos + ref_len + flank); for odd w the whole region is reverse-complemented
+ *   with the reference's comp_table. On a window-table handle flank must be 0 (DRM_ERR_ARG) and the region is the
+ *   table row (empty for an id outside the table). ref_len + 2 * flank > 256 or a query longer than 256 is
+ *   DRM_ERR_UNSUPPORTED. Rows i = 1..n run over the region, columns j = 1..m over the query bytes as passed (tags
+ *   included); equality is raw byte equality.
+ * Recurrence (Gotoh), borders H = 0, E = F = -inf, open / ext = gap_open / gap_extend:
+ *   F[i][j] = max(H[i-1][j] - open - ext, F[i-1][j] - ext)      (a run of region bytes: D)
+ *   E[i][j] = max(H[i][j-1] - open - ext, E[i][j-1] - ext)      (a run of query bytes: I)
+ *   H[i][j] = max(0, H[i-1][j-1] + s, F[i][j], E[i][j])         s = +match on equal bytes, else -mismatch
+ *   score = max H. End cell: among H == score the smallest i, then the smallest j (drm_sw_align's rule).
+ * Traceback from the end cell in state H:
+ *   State H: stop when H[i][j] == 0, i == 0 or j == 0; otherwise the first true condition decides:
+ *     1. H[i][j] == H[i-1][j-1] + s -> M, both step back   2. H[i][j] == F[i][j] -> state F at the same cell
+ *     3. otherwise -> state E at the same cell.
+ *   State F: emit D; if F[i][j] == H[i-1][j] - open - ext the next state is H (closing the gap wins a tie against
+ *     extending it), otherwise it stays F; then i -= 1.
+ *   State E: the same with I, H[i][j-1] and j -= 1.
+ * The record is drm_sw_alignment's: ref_begin / ref_end are relative to the region, nm = mismatching M columns +
+ * inserted + deleted bases, operation words and the status 2 rule as for drm_sw_align; ops_stride = q_len + region
+ * length never overflows. With {1, 1, 0, 1} and flank 0 the result equals drm_sw_align's, record and words: at
+ * open = 0 the closing move is always available, so the walk decides again with M first at every cell. */
+typedef struct {
+    int32_t match, mismatch, gap_open, gap_extend;
+} drm_sw_scoring;
+/* drm_sw_align's arguments after the scoring and the flank. Host pointers. */
+int drm_sw_align_affine(drm_refs *refs, const drm_sw_scoring *scoring, int32_t flank, const uint64_t *window_ids,
+                        const int64_t *pair_query, int64_t npairs, const uint8_t *queries, const int32_t *q_len,
+                        int32_t q_stride, int64_t nq, drm_sw_alignment *out, uint32_t *ops, int32_t ops_stride);
+/* Device-buffer form, enqueued on `stream`; query lengths are bounded by q_stride (<= 256). */
+int drm_sw_align_affine_device(drm_refs *refs, const drm_sw_scoring *scoring, int32_t flank,
+                               const uint64_t *d_window_ids, const int64_t *d_pair_query, int64_t npairs,
+                               const uint8_t *d_queries, const int32_t *d_q_len, int32_t q_stride, int64_t nq,
+                               drm_sw_alignment *d_out, uint32_t *d_ops, int32_t ops_stride, void *stream);
+/* Host only: the target region of one window id on a genome handle (DRM_ERR_ARG on a window table or a negative
+ * flank, DRM_ERR_UNSUPPORTED when ref_len + 2 * flank > 256): genome[*start, *start + *len), *reverse = 1 when it is
+ * reverse-complemented. A window past the genome end has *len = 0 (and *start = 0). */
+int drm_sw_align_region(const drm_refs *refs, uint64_t window_id, int32_t flank, int64_t *start, int32_t *len,
+                        int32_t *reverse);
+/* Host only: drm_sam_cigar for a record whose ref_begin / ref_end are relative to a region: *pos1 = region_start +
+ * (reverse ? region_len - ref_end : ref_begin) + 1, the CIGAR reversed, clips included, when reverse != 0.
+ * drm_sam_cigar is the case (window_id / 2, ref_len, window_id & 1). The same errors. */
+int drm_sam_cigar_region(const drm_sw_alignment *a, const uint32_t *ops, int32_t q_len, int32_t tag_prefix,
+                         int32_t tag_postfix, int64_t region_start, int32_t region_len, int32_t reverse,
+                         int64_t *pos1, char *cigar, int32_t cigar_cap);
+
 /* ---------------------------------------------------------------- L2 rerank (the reference's live path)
  * post_process_l2_static (src/utils/post_processor.cpp:1023-1162, called at src/main.cpp:330) ->
  * find_sequences (static) -> Vectorizer::vectorize of the candidate windows -> batch_reranker(k = k_clusters)

@@ -12,7 +12,9 @@
 // instead of the static window table); use_streaming writes <output_dir>/results.sam block by block
 // (write_sam_streaming) and, like the reference, skips the .npy outputs -- the reference streams only in
 // its dynamic branch, so static + streaming writes no result file there either. DRM_SAM_CIGAR=1 replaces the
-// reference's pseudo POS / CIGAR in that SAM by the GPU alignment of every row (drm_sw_align).
+// reference's pseudo POS / CIGAR in that SAM by the GPU alignment of every row (drm_sw_align); with
+// DRM_SAM_SCORING=match,mismatch,open,extend and / or DRM_SAM_FLANK=n beside it, by the affine-gap alignment over the
+// window widened by n genome bases on either side (drm_sw_align_affine).
 // Sequence inputs are embedded by the reference's GRU model on the GPU (drm_vectorize) when
 // DRM_ENCODER names it (.xml IR or .drmenc) or when the reference's models/ path exists in the working
 // directory (Config::Inference::MODEL_PATH); otherwise by the deterministic 3-mer stand-in. The rerank is
@@ -59,16 +61,35 @@ template <class T> struct Pinned {
 
 // DRM_SAM_CIGAR=1: the GPU alignments (drm_sw_align) of one SAM block's rows, ids[i * k + j] for j < cnt[i] against
 // query lo + i. The first pass keeps 16 operation words per row; the rows that need more (status 2) are aligned
-// again as a sub-list with a stride that cannot overflow. Rows past cnt[i] keep an empty record.
+// again as a sub-list with a stride that cannot overflow. Rows past cnt[i] keep an empty record. With `affine` the
+// rows are aligned by drm_sw_align_affine over their flanked regions, which are kept for the formatter.
+struct AffineMode {
+    drm_sw_scoring scoring;
+    int32_t flank;
+};
 struct BlockAlignments {
     std::vector<drm_sw_alignment> rec;
     std::vector<uint32_t> ops;
-    std::vector<int64_t> off;
-    drm::SamAlignments view() const { return {rec.data(), ops.data(), off.data()}; }
+    std::vector<int64_t> off, region_start;
+    std::vector<int32_t> region_len;
+    drm::SamAlignments view() const
+    {
+        drm::SamAlignments v{rec.data(), ops.data(), off.data()};
+        if (!region_start.empty()) {
+            v.region_start = region_start.data();
+            v.region_len = region_len.data();
+        }
+        return v;
+    }
 
     void align(drm_refs *rt, const uint64_t *ids, const int32_t *cnt, size_t m, size_t k, const uint8_t *queries,
-               const int32_t *q_len, int32_t q_stride, int32_t ref_len)
+               const int32_t *q_len, int32_t q_stride, int32_t ref_len, const AffineMode *affine)
     {
+        auto run = [&](const uint64_t *w, const int64_t *q, size_t n, drm_sw_alignment *r, uint32_t *o, int32_t stride) {
+            return affine ? drm_sw_align_affine(rt, &affine->scoring, affine->flank, w, q, (int64_t)n, queries, q_len,
+                                                q_stride, (int64_t)m, r, o, stride)
+                          : drm_sw_align(rt, w, q, (int64_t)n, queries, q_len, q_stride, (int64_t)m, r, o, stride);
+        };
         constexpr int32_t kStride = 16;
         constexpr size_t kChunk = (size_t)1 << 20; // pairs per launch
         std::vector<uint64_t> wid;
@@ -86,8 +107,7 @@ struct BlockAlignments {
         std::vector<uint32_t> o1(np * kStride);
         for (size_t c = 0; c < np; c += kChunk) {
             const size_t nc = std::min(kChunk, np - c);
-            check(drm_sw_align(rt, wid.data() + c, pq.data() + c, (int64_t)nc, queries, q_len, q_stride, (int64_t)m,
-                               r1.data() + c, o1.data() + c * kStride, kStride));
+            check(run(wid.data() + c, pq.data() + c, nc, r1.data() + c, o1.data() + c * kStride, kStride));
         }
         std::vector<uint64_t> wid2;
         std::vector<int64_t> pq2, idx2;
@@ -97,13 +117,12 @@ struct BlockAlignments {
                 pq2.push_back(pq[p]);
                 idx2.push_back((int64_t)p);
             }
-        const int32_t full = q_stride + ref_len;
+        const int32_t full = q_stride + ref_len + (affine ? 2 * affine->flank : 0);
         std::vector<drm_sw_alignment> r2(wid2.size());
         std::vector<uint32_t> o2(wid2.size() * (size_t)full);
         for (size_t c = 0; c < wid2.size(); c += kChunk) {
             const size_t nc = std::min(kChunk, wid2.size() - c);
-            check(drm_sw_align(rt, wid2.data() + c, pq2.data() + c, (int64_t)nc, queries, q_len, q_stride, (int64_t)m,
-                               r2.data() + c, o2.data() + c * (size_t)full, full));
+            check(run(wid2.data() + c, pq2.data() + c, nc, r2.data() + c, o2.data() + c * (size_t)full, full));
         }
         ops.clear();
         size_t x2 = 0;
@@ -116,8 +135,64 @@ struct BlockAlignments {
             off[(size_t)row[p]] = (int64_t)ops.size();
             ops.insert(ops.end(), o, o + r.n_ops);
         }
+        if (affine) {
+            region_start.assign(m * k, 0);
+            region_len.assign(m * k, 0);
+            for (size_t p = 0; p < np; ++p) {
+                int32_t rev = 0;
+                check(drm_sw_align_region(rt, wid[p], affine->flank, &region_start[(size_t)row[p]],
+                                          &region_len[(size_t)row[p]], &rev));
+            }
+        }
     }
 };
+
+// DRM_SAM_SCORING=match,mismatch,open,extend and DRM_SAM_FLANK=n (with DRM_SAM_CIGAR=1 only): strictly parsed, and
+// checked against drm_sw_align_affine's ranges before any work. A flank alone means the scoring 1,1,0,1.
+static bool parse_int(const std::string &t, long &v)
+{
+    if (t.empty() || t.size() > 9 || t.find_first_not_of("0123456789") != std::string::npos)
+        return false;
+    v = std::stol(t);
+    return true;
+}
+
+static bool affine_mode_from_env(size_t ref_len, AffineMode &mode)
+{
+    const char *sc = std::getenv("DRM_SAM_SCORING"), *fl = std::getenv("DRM_SAM_FLANK");
+    if (!sc && !fl)
+        return false;
+    mode = AffineMode{{1, 1, 0, 1}, 0};
+    if (sc) {
+        std::vector<long> v;
+        const std::string s(sc);
+        for (size_t p = 0; p <= s.size();) {
+            size_t q = s.find(',', p);
+            if (q == std::string::npos)
+                q = s.size();
+            long x = 0;
+            if (!parse_int(s.substr(p, q - p), x))
+                throw drm::Error(DRM_ERR_ARG, "DRM_SAM_SCORING must be match,mismatch,open,extend (four non-negative "
+                                              "integers): \"" + s + "\"");
+            v.push_back(x);
+            p = q + 1;
+        }
+        if (v.size() != 4 || v[0] < 1 || v[0] > 31 || v[1] < 1 || v[1] > 63 || v[2] > 63 || v[3] < 1 || v[3] > 63)
+            throw drm::Error(DRM_ERR_ARG, "DRM_SAM_SCORING must be match,mismatch,open,extend with match 1..31, "
+                                          "mismatch 1..63, open 0..63, extend 1..63: \"" + s + "\"");
+        mode.scoring = drm_sw_scoring{(int32_t)v[0], (int32_t)v[1], (int32_t)v[2], (int32_t)v[3]};
+    }
+    if (fl) {
+        long x = 0;
+        if (!parse_int(fl, x))
+            throw drm::Error(DRM_ERR_ARG, std::string("DRM_SAM_FLANK must be a non-negative integer: \"") + fl + "\"");
+        if (ref_len + 2 * (size_t)x > 256)
+            throw drm::Error(DRM_ERR_UNSUPPORTED, "DRM_SAM_FLANK " + std::to_string(x) + ": ref_len " +
+                                                      std::to_string(ref_len) + " + 2 * flank > 256");
+        mode.flank = (int32_t)x;
+    }
+    return true;
+}
 
 int main(int argc, char *argv[])
 {
@@ -159,6 +234,9 @@ int main(int argc, char *argv[])
         const bool use_dynamic = argc >= 9 && std::stoi(argv[8]) != 0;
         const bool use_streaming = argc >= 10 && std::stoi(argv[9]) != 0;
         const std::string sam_file = out_dir + "/results.sam"; // src/main.cpp:67
+        AffineMode affine_mode{};
+        const bool cigar_env = std::getenv("DRM_SAM_CIGAR") && std::atoi(std::getenv("DRM_SAM_CIGAR")) != 0;
+        const AffineMode *affine = cigar_env && affine_mode_from_env(ref_len, affine_mode) ? &affine_mode : nullptr;
         // devices: DRM_DEVICES=0,1,... fans the batch out over several GPUs (contiguous query shards,
         // replicated index); DRM_DEVICE=i picks one (default 0)
         std::vector<int> devices;
@@ -428,7 +506,7 @@ int main(int argc, char *argv[])
                     drm::SamAlignments av{};
                     if (sam_cigar) {
                         ba.align(art, l2i.data() + lo * k, cnt.data() + lo, m, (size_t)k, qbuf.p + lo * qs, ql.p + lo,
-                                 (int32_t)qs, (int32_t)ref_len);
+                                 (int32_t)qs, (int32_t)ref_len, affine);
                         av = ba.view();
                     }
                     drm::write_sam_block(sam_file, lo == 0, "ref", ref_len, qseqs, qids, lo, m, l2i.data() + lo * k,
@@ -465,7 +543,7 @@ int main(int argc, char *argv[])
                     if (sam_cigar) {
                         try {
                             ba->align(art, rows, cnt->data(), m, kr, qbuf.p + lo * qs, ql.p + lo, (int32_t)qs,
-                                      (int32_t)ref_len);
+                                      (int32_t)ref_len, affine);
                         } catch (...) {
                             if (writer.joinable())
                                 writer.join();

@@ -2,7 +2,10 @@
 152-byte tagged reads at 1 % substitutions, each read aligned to the window it was drawn from. HIP events, warm,
 median of --runs runs. For scale it also times the score-only rerank (drm_post_process_sw_static_device) on the same
 pairs (one candidate per read, which leaves most of that kernel's lanes idle) and on as many pairs in the shape it
-is built for (P / 128 reads x 128 candidates). Checks the alignment scores against the rerank's before timing."""
+is built for (P / 128 reads x 128 candidates). Checks the alignment scores against the rerank's before timing.
+--scoring match,mismatch,open,extend adds the affine kernel (drm_sw_align_affine_device) on the same pairs in the same
+process: at flank 0 on the same window table, and at --flank on a genome handle of the same genome (the same window
+ids). The timed functions take turns run by run, so that a drift of the machine meets all of them alike."""
 import argparse
 import statistics
 import sys
@@ -10,15 +13,17 @@ import sys
 import numpy as np
 
 sys.path.insert(0, ".")
-from deepreadmapper_amd import WindowTable, synth  # noqa: E402
+from deepreadmapper_amd import GenomeTable, WindowTable, synth  # noqa: E402
 from deepreadmapper_amd._native import check, lib  # noqa: E402
 from deepreadmapper_amd.device import DeviceBuffer, Event, Stream  # noqa: E402
-from deepreadmapper_amd.rerank import SW_ALIGNMENT_DTYPE  # noqa: E402
+from deepreadmapper_amd.rerank import SW_ALIGNMENT_DTYPE, sw_scoring  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--pairs", type=int, default=65_536)
-ap.add_argument("--runs", type=int, default=7)
+ap.add_argument("--runs", type=int, default=9)
 ap.add_argument("--ops-stride", type=int, default=16)
+ap.add_argument("--scoring", default=None, help="match,mismatch,open,extend: also time the affine kernel")
+ap.add_argument("--flank", type=int, default=8, help="flank of the affine kernel's second timing (genome handle)")
 a = ap.parse_args()
 P, K = a.pairs, 128
 
@@ -57,18 +62,28 @@ def rerank_native_shape():
                                                   K, d_sc2.ptr, d_id2.ptr, d_st2.ptr, st.handle))
 
 
-def timed(f):
-    f()  # warm
-    st.synchronize()
-    ts = []
-    for _ in range(a.runs):
-        e0, e1 = Event(), Event()
-        e0.record(st)
+def affine(handle, flank):
+    def f():
+        check(lib().drm_sw_align_affine_device(handle, scoring.ctypes.data, flank, d_wid.ptr, d_pq.ptr, P, d_q.ptr,
+                                               d_ql.ptr, q.shape[1], P, d_rec.ptr, d_ops.ptr, a.ops_stride, st.handle))
+    return f
+
+
+def timed(fs):
+    """Median / min / max of --runs runs per function, warm, the functions taking turns."""
+    for f in fs:
         f()
-        e1.record(st)
-        st.synchronize()
-        ts.append(e0.elapsed_ms(e1))
-    return statistics.median(ts), min(ts), max(ts)
+    st.synchronize()
+    ts = [[] for _ in fs]
+    for _ in range(a.runs):
+        for x, f in enumerate(fs):
+            e0, e1 = Event(), Event()
+            e0.record(st)
+            f()
+            e1.record(st)
+            st.synchronize()
+            ts[x].append(e0.elapsed_ms(e1))
+    return [(statistics.median(t), min(t), max(t)) for t in ts]
 
 
 align()
@@ -79,9 +94,24 @@ assert np.array_equal(rec["score"], d_sc1.download().reshape(-1)), "alignment sc
 assert (rec["status"] == 0).all(), "a read did not align (or needed more than --ops-stride operations)"
 print(f"{P} pairs, 150 B windows x {q.shape[1]} B reads; scores equal the rerank's; mean score "
       f"{rec['score'].mean():.1f}, mean n_ops {rec['n_ops'].mean():.2f}", flush=True)
-for name, f, n in (("sw_align (DP + traceback)", align, P), ("score-only rerank, same pairs (1 candidate / read)",
-                                                           rerank_same_pairs, P),
-                   (f"score-only rerank, {nq2} reads x {K} candidates", rerank_native_shape, nq2 * K)):
-    med, lo, hi = timed(f)
+jobs = [("sw_align (DP + traceback)", align, P), ("score-only rerank, same pairs (1 candidate / read)",
+                                                 rerank_same_pairs, P),
+        (f"score-only rerank, {nq2} reads x {K} candidates", rerank_native_shape, nq2 * K)]
+if a.scoring:
+    scoring = sw_scoring(a.scoring.split(","))
+    gtable = GenomeTable(g, 150)
+    for handle, flank in ((table.handle, 0), (gtable.handle, a.flank)):
+        affine(handle, flank)()
+        st.synchronize()
+        rec = d_rec.download()
+        assert (rec["status"] == 0).all(), "a read did not align under the affine scoring"
+        print(f"affine {a.scoring} flank {flank}: mean score {rec['score'].mean():.1f}, mean n_ops "
+              f"{rec['n_ops'].mean():.2f}, {int((rec['q_end'] - rec['q_begin'] == 150).sum())} of {P} reads aligned "
+              f"end to end", flush=True)
+        jobs.append((f"sw_align_affine {a.scoring} flank {flank}", affine(handle, flank), P))
+res = timed([f for _, f, _ in jobs])
+for (name, _, n), (med, lo, hi) in zip(jobs, res):
     print(f"{name}: median {med:.3f} ms (min {lo:.3f}, max {hi:.3f}, {a.runs} runs) = {n / med / 1e3:.2f} M pairs/s",
           flush=True)
+if a.scoring:
+    print(f"affine / linear: flank 0 {res[3][0] / res[0][0]:.2f}x, flank {a.flank} {res[4][0] / res[0][0]:.2f}x", flush=True)
