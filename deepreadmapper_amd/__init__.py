@@ -11,7 +11,9 @@ from .rerank import (WindowTable, calc_sw_score, calc_sw_scores, post_process_sw
                      l2_rerank_dynamic_arrays, post_process_l2_dynamic, sw_align_arrays, sam_cigar,
                      SW_ALIGNMENT_DTYPE, sw_align_affine_arrays, sw_align_region, sam_cigar_region)
 
-__version__ = "0.3.0"
+from .pairing import PAIR_RESULT_DTYPE, pair_hits, pair_hits_device, sam_pair_fields  # noqa: F401  (paired-end reads)
+
+__version__ = "0.4.0"
 from .executor import Comm, MultiIndex, search_rerank  # noqa: F401  (batch executor, multi-GPU, RCCL gather)
 from .exact import QUERY_TILE, exact_search_l2, recall_at_k, set_slice_rows  # noqa: F401  (exhaustive scans, recall@k)
 from .encoder import Encoder, Preprocessor, Vectorizer, export_encoder  # noqa: F401  (GRU read encoder)

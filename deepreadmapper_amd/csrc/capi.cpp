@@ -256,7 +256,7 @@ void free_index(drm::DeviceIndex &d)
 extern "C" {
 
 const char *drm_last_error(void) { return drm::g_last_error.c_str(); }
-int drm_version(void) { return 300; /* 0.3.0 */ }
+int drm_version(void) { return 400; /* 0.4.0 */ }
 
 int drm_device_count(int *n)
 {
@@ -1851,6 +1851,89 @@ int drm_sw_align_region(const drm_refs *refs, uint64_t window_id, int32_t flank,
         const int64_t e = std::min<int64_t>((int64_t)pos + refs->dev.ref_len + flank, refs->dev.glen);
         *start = s;
         *len = (int32_t)(e - s);
+    });
+}
+
+// ---------------------------------------------------------------------- mate pairing (pair_hits.hip)
+static drm::PairArgs make_pair_args(const drm_pair_params *p, const uint64_t *ids1, const int32_t *scores1,
+                                    const int32_t *cnt1, const uint64_t *ids2, const int32_t *scores2,
+                                    const int32_t *cnt2, int64_t npairs, int32_t k, int64_t row_step,
+                                    drm_pair_result *out)
+{
+    if (!p)
+        throw Error(DRM_ERR_ARG, "null pair parameters");
+    if (k < 0 || k > drm::kMaxCands)
+        throw Error(DRM_ERR_UNSUPPORTED, "k = " + std::to_string(k) + " outside [0, 1024], the rerank's candidate cap");
+    if (p->ref_len < 1 || p->ref_len > (1 << 20))
+        throw Error(DRM_ERR_ARG, "ref_len " + std::to_string(p->ref_len) + " outside [1, 2^20]");
+    if (p->min_tlen < 0 || p->min_tlen > p->max_tlen || p->max_tlen > (1 << 30))
+        throw Error(DRM_ERR_ARG, "template lengths [" + std::to_string(p->min_tlen) + ", " +
+                                     std::to_string(p->max_tlen) + "] must satisfy 0 <= min <= max <= 2^30");
+    if (p->unpaired_penalty < 0 || p->unpaired_penalty > (1 << 20))
+        throw Error(DRM_ERR_ARG, "unpaired_penalty " + std::to_string(p->unpaired_penalty) + " outside [0, 2^20]");
+    if (npairs < 0 || row_step < 1)
+        throw Error(DRM_ERR_ARG, "npairs must be >= 0 and row_step >= 1");
+    if (npairs > 0 && (!cnt1 || !cnt2 || !out || (k > 0 && (!ids1 || !scores1 || !ids2 || !scores2))))
+        throw Error(DRM_ERR_ARG, "null argument");
+    return drm::PairArgs{*p, ids1, scores1, cnt1, ids2, scores2, cnt2, npairs, k, row_step, out};
+}
+
+int drm_pair_hits_device(const drm_pair_params *p, const uint64_t *d_ids1, const int32_t *d_scores1,
+                         const int32_t *d_cnt1, const uint64_t *d_ids2, const int32_t *d_scores2,
+                         const int32_t *d_cnt2, int64_t npairs, int32_t k, int64_t row_step, drm_pair_result *d_out,
+                         void *stream)
+{
+    return guarded([&] {
+        const drm::PairArgs a = make_pair_args(p, d_ids1, d_scores1, d_cnt1, d_ids2, d_scores2, d_cnt2, npairs, k,
+                                               row_step, d_out);
+        drm::launch_pair_hits(a, (hipStream_t)stream);
+    });
+}
+
+int drm_pair_hits(const drm_pair_params *p, const uint64_t *ids1, const int32_t *scores1, const int32_t *cnt1,
+                  const uint64_t *ids2, const int32_t *scores2, const int32_t *cnt2, int64_t npairs, int32_t k,
+                  int64_t row_step, drm_pair_result *out)
+{
+    return guarded([&] {
+        drm::PairArgs a = make_pair_args(p, ids1, scores1, cnt1, ids2, scores2, cnt2, npairs, k, row_step, out);
+        if (npairs == 0)
+            return;
+        // the counted rows' scores, before anything reaches the device
+        for (int m = 0; m < 2; ++m) {
+            const int32_t *cnt = m ? cnt2 : cnt1, *sc = m ? scores2 : scores1;
+            for (int64_t q = 0; q < npairs; ++q) {
+                const int64_t row = q * row_step;
+                const int32_t c = std::min(std::max(cnt[row], 0), k);
+                for (int32_t j = 0; j < c; ++j)
+                    if (sc[row * k + j] < 0 || sc[row * k + j] > (1 << 20))
+                        throw Error(DRM_ERR_ARG, "pair " + std::to_string(q) + ", mate " + std::to_string(m + 1) +
+                                                     ", row " + std::to_string(j) + ": score " +
+                                                     std::to_string(sc[row * k + j]) + " outside [0, 2^20]");
+            }
+        }
+        // each mate's lists span ((npairs - 1) * row_step + 1) rows from its own base pointer (the two may overlap)
+        const size_t rows = (size_t)(npairs - 1) * (size_t)row_step + 1;
+        DevBuf<uint64_t> di1(rows * (size_t)k), di2(rows * (size_t)k);
+        DevBuf<int32_t> ds1(rows * (size_t)k), ds2(rows * (size_t)k), dc1(rows), dc2(rows);
+        DevBuf<drm_pair_result> dout((size_t)npairs);
+        if (k > 0) {
+            di1.upload(ids1);
+            di2.upload(ids2);
+            ds1.upload(scores1);
+            ds2.upload(scores2);
+        }
+        dc1.upload(cnt1);
+        dc2.upload(cnt2);
+        a.ids1 = di1.p;
+        a.ids2 = di2.p;
+        a.scores1 = ds1.p;
+        a.scores2 = ds2.p;
+        a.cnt1 = dc1.p;
+        a.cnt2 = dc2.p;
+        a.out = dout.p;
+        drm::launch_pair_hits(a, nullptr);
+        DRM_HIP_CHECK(hipDeviceSynchronize());
+        dout.download(out);
     });
 }
 

@@ -315,6 +315,22 @@ struct AffineAlignArgs {
 };
 void launch_sw_align_affine(const DeviceRefs &refs, AffineAlignArgs a, int max_qlen, hipStream_t stream);
 
+// Mate pairing of two reads' reranked hit lists (pair_hits.hip; drm_pair_hits): one wave per
+// pair; pair p's mate-m list is ids_m / scores_m + p * row_step * k with the count cnt_m[p * row_step]. Runs on the
+// current device; throws Error(DRM_ERR_UNSUPPORTED) for k outside [0, kMaxCands].
+struct PairArgs {
+    drm_pair_params prm;
+    const uint64_t *ids1;
+    const int32_t *scores1, *cnt1;
+    const uint64_t *ids2;
+    const int32_t *scores2, *cnt2;
+    int64_t npairs;
+    int32_t k;
+    int64_t row_step;
+    drm_pair_result *out; // [npairs]
+};
+void launch_pair_hits(const PairArgs &a, hipStream_t stream);
+
 // L2 rerank (post_process_l2_static -> batch_reranker, src/utils/post_processor.cpp:1023-1162,
 // src/utils/reranker.cpp:98-195): distances from the window embedding table, libstdc++ partial_sort
 struct L2Args {

@@ -159,6 +159,17 @@ void write_sam_block(const std::string &path, bool header, const std::string &re
                      const std::vector<std::string> &query_seqs, const std::vector<std::string> &query_ids,
                      size_t q0, size_t nq, const uint64_t *ids, const int32_t *counts, size_t k,
                      const SamAlignments *aln = nullptr);
+// The paired form (DRM_MATES, no reference counterpart): the two primary lines of pairs whose reads are queries
+// q0 + 2 * p (mate 1) and q0 + 2 * p + 1 (mate 2). Row r = 2 * p + m of the block carries the read's chosen window
+// ids[r] (counts[r] = 1, or 0 for a read without a hit) and its alignment aln.rec[r] as in the DRM_SAM_CIGAR mode
+// (one row per read); a read without a hit or with a status-1 record is unmapped. proper[p] != 0: drm_pair_hits
+// chose a proper combination. The fields that relate the two lines are drm_sam_pair_fields' (include/drm_hip.h):
+//   mapped:   QNAME FLAG ref POS 60 CIGAR = PNEXT TLEN SEQ * AS:i:<score> NM:i:<nm>
+//   unmapped: QNAME FLAG ref|* POS 60 * =|* PNEXT TLEN SEQ *        (SEQ as read; "*" when neither mate is mapped)
+void write_sam_pairs(const std::string &path, bool header, const std::string &ref_name, size_t ref_len,
+                     const std::vector<std::string> &query_seqs, const std::vector<std::string> &query_ids,
+                     size_t q0, size_t npairs, const uint64_t *ids, const int32_t *counts, const int32_t *proper,
+                     const SamAlignments &aln);
 
 void build_hnswpq(const float *x, int64_t n, int d, int M_pq, int nbits, int M_hnsw, int efc, double sample_rate,
                   int nthreads, uint64_t seed, const std::string &path);

@@ -489,6 +489,123 @@ void drm::write_sam_block(const std::string &path, bool header, const std::strin
     out << buf;
 }
 
+// ----------------------------------------------------------------------- paired SAM (include/drm_hip.h)
+static void sam_pair_fields(const drm_sam_mate in[2], bool proper, drm_sam_mate_fields out[2])
+{
+    using drm::Error;
+    for (int m = 0; m < 2; ++m)
+        if (in[m].mapped && (in[m].pos1 < 1 || in[m].ref_span < 1))
+            throw Error(DRM_ERR_ARG, "mate " + std::to_string(m + 1) + " is mapped with pos1 " +
+                                         std::to_string(in[m].pos1) + ", ref_span " + std::to_string(in[m].ref_span) +
+                                         ": both must be >= 1");
+    const bool both = in[0].mapped && in[1].mapped, any = in[0].mapped || in[1].mapped;
+    int64_t len = 0;
+    if (both)
+        len = std::max(in[0].pos1 + in[0].ref_span - 1, in[1].pos1 + in[1].ref_span - 1) -
+              std::min(in[0].pos1, in[1].pos1) + 1;
+    for (int m = 0; m < 2; ++m) {
+        const drm_sam_mate &self = in[m], &mate = in[1 - m];
+        drm_sam_mate_fields &o = out[m];
+        o.flag = 0x1 | (m == 0 ? 0x40 : 0x80) | (self.mapped ? 0 : 0x4) | (mate.mapped ? 0 : 0x8) |
+                 (self.mapped && self.reverse ? 0x10 : 0) | (mate.mapped && mate.reverse ? 0x20 : 0) |
+                 (proper && both ? 0x2 : 0);
+        o.has_rname = any ? 1 : 0;
+        o.pos = self.mapped ? self.pos1 : mate.mapped ? mate.pos1 : 0;
+        o.pnext = mate.mapped ? mate.pos1 : self.mapped ? self.pos1 : 0;
+        const bool left = self.pos1 < mate.pos1 || (self.pos1 == mate.pos1 && m == 0);
+        o.tlen = both ? (left ? len : -len) : 0;
+    }
+}
+
+extern "C" int drm_sam_pair_fields(const drm_sam_mate in[2], int proper, drm_sam_mate_fields out[2])
+{
+    try {
+        if (!in || !out)
+            throw drm::Error(DRM_ERR_ARG, "null argument");
+        sam_pair_fields(in, proper != 0, out);
+        return DRM_OK;
+    } catch (const drm::Error &e) {
+        drm::set_last_error(e.what());
+        return e.code;
+    } catch (const std::exception &e) {
+        drm::set_last_error(e.what());
+        return DRM_ERR_ARG;
+    }
+}
+
+void drm::write_sam_pairs(const std::string &path, bool header, const std::string &ref_name, size_t ref_len,
+                          const std::vector<std::string> &query_seqs, const std::vector<std::string> &query_ids,
+                          size_t q0, size_t npairs, const uint64_t *ids, const int32_t *counts, const int32_t *proper,
+                          const SamAlignments &aln)
+{
+    std::ofstream out(path, header ? std::ios::out : std::ios::app);
+    if (!out.is_open())
+        throw Error(DRM_ERR_IO, "Failed to open SAM file: " + path);
+    if (header) {
+        out << "@HD\tVN:1.0\tSO:unsorted\n";
+        out << "@SQ\tSN:" << ref_name << "\tLN:" << ref_len << "\n";
+    }
+    std::string buf;
+    for (size_t p = 0; p < npairs; ++p) {
+        drm_sam_mate in[2];
+        drm_sam_mate_fields f[2];
+        std::string cigar[2], clean[2];
+        for (int m = 0; m < 2; ++m) {
+            const size_t row = 2 * p + (size_t)m;
+            const std::string &tagged = query_seqs[q0 + row];
+            // the read is the query without format_fastq's tags, as in the DRM_SAM_CIGAR row
+            const int pre = !tagged.empty() && tagged.front() == '<', post = tagged.size() > 1 && tagged.back() == '>';
+            clean[m] = tagged.substr((size_t)pre, tagged.size() - (size_t)pre - (size_t)post);
+            const drm_sw_alignment &a = aln.rec[row];
+            in[m] = drm_sam_mate{0, 0, 0, 0};
+            if (counts[row] < 1 || a.status == 1)
+                continue;
+            const uint64_t sid = ids[row];
+            int64_t pos1 = 0;
+            if (aln.region_start)
+                sam_cigar(a, aln.ops + aln.ops_off[row], (int32_t)tagged.size(), pre, post, aln.region_start[row],
+                          aln.region_len[row], (sid & 1u) != 0, pos1, cigar[m]);
+            else
+                sam_cigar(a, aln.ops + aln.ops_off[row], (int32_t)tagged.size(), pre, post, (int64_t)(sid / 2),
+                          (int32_t)ref_len, (sid & 1u) != 0, pos1, cigar[m]);
+            in[m] = drm_sam_mate{1, (int32_t)(sid & 1u), pos1, a.ref_end - a.ref_begin};
+        }
+        sam_pair_fields(in, proper[p] != 0, f);
+        const size_t g = q0 + 2 * p;
+        const std::string qname = (g < query_ids.size() && !query_ids[g].empty()) ? query_ids[g]
+                                                                                  : "S1/" + std::to_string(g / 2 + 1) + "/0";
+        for (int m = 0; m < 2; ++m) {
+            buf += qname;
+            buf += '\t';
+            buf += std::to_string(f[m].flag);
+            buf += '\t';
+            buf += f[m].has_rname ? ref_name : std::string("*");
+            buf += '\t';
+            buf += std::to_string(f[m].pos);
+            buf += "\t60\t";
+            buf += in[m].mapped ? cigar[m] : std::string("*");
+            buf += f[m].has_rname ? "\t=\t" : "\t*\t";
+            buf += std::to_string(f[m].pnext);
+            buf += '\t';
+            buf += std::to_string(f[m].tlen);
+            buf += '\t';
+            buf += clean[m].empty() ? std::string("*")
+                                    : (in[m].mapped && in[m].reverse) ? drm::reverse_complement(clean[m]) : clean[m];
+            buf += "\t*";
+            if (in[m].mapped) {
+                buf += "\tAS:i:" + std::to_string(aln.rec[2 * p + (size_t)m].score);
+                buf += "\tNM:i:" + std::to_string(aln.rec[2 * p + (size_t)m].nm);
+            }
+            buf += '\n';
+        }
+        if (buf.size() > (1u << 22)) {
+            out << buf;
+            buf.clear();
+        }
+    }
+    out << buf;
+}
+
 extern "C" int drm_extract_fasta_sequence(const char *path, uint8_t *out, int64_t *len)
 {
     try {

@@ -384,6 +384,71 @@ int drm_sam_cigar_region(const drm_sw_alignment *a, const uint32_t *ops, int32_t
                          int32_t tag_postfix, int64_t region_start, int32_t region_len, int32_t reverse,
                          int64_t *pos1, char *cigar, int32_t cigar_cap);
 
+/* ---------------------------------------------------------------- Mate pairing (paired-end reads)
+ * Which hit of mate 1 and which hit of mate 2 belong to one fragment. The reference maps single reads only (its SAM
+ * prints "* 0 0" in RNEXT / PNEXT / TLEN), so this text is the definition.
+ * A hit is a row (w, s) of a read's rerank output (top_ids / top_scores): pos(w) = w >> 1 (int64), rev(w) = w & 1.
+ * Only the first `count` rows of a list take part, a count outside [0, k] being clamped (a negative rerank status is
+ * 0 rows), and of those only the live ones, s > 0: a zero-score row is an out-of-genome window. Row indices j always
+ * refer to the original list. A mate's top hit is its live row of largest s, the smallest row among equals (the list
+ * need not be sorted).
+ * A proper combination (FR library orientation, the only one supported): row j1 of mate 1 with row j2 of mate 2 is
+ * proper iff both rows are live, their rev differs, and with f the forward and r the reverse hit pos(f) <= pos(r) and
+ * min_tlen <= T <= max_tlen (both inclusive), T = pos(r) + ref_len - pos(f) in 64-bit arithmetic: any u64 window id
+ * is safe.
+ * Choice: n_proper = the number of proper combinations (always reported). The best proper combination maximises
+ * s1 + s2, then takes the smallest j1, then the smallest j2. With t1, t2 the mates' top hits:
+ *   status 0: both mates live, a proper combination exists and best_sum >= s(t1) + s(t2) - unpaired_penalty:
+ *             (j1, j2) = the best proper combination, score = its sum, tlen = its T;
+ *   status 1: both mates live, otherwise: (j1, j2) = (t1, t2), score = s(t1) + s(t2), tlen = 0;
+ *   status 2: only mate 1 live: j1 = t1, j2 = -1, score = s(t1), tlen = 0;
+ *   status 3: only mate 2 live: j1 = -1, j2 = t2, score = s(t2), tlen = 0;
+ *   status 4: neither live: j1 = j2 = -1, score = 0, tlen = 0.
+ * Arguments: 0 <= k <= 1024 (beyond: DRM_ERR_UNSUPPORTED; 1024 is the rerank's candidate cap), 1 <= ref_len <= 2^20,
+ * 0 <= min_tlen <= max_tlen <= 2^30, 0 <= unpaired_penalty <= 2^20, row_step >= 1, npairs >= 0 (DRM_ERR_ARG
+ * otherwise). Scores of the counted rows must lie in [0, 2^20]: the host entry point checks it (DRM_ERR_ARG), for the
+ * device form it is the caller's contract (the rerank's scores are at most the read length).
+ * Layout: row_step is the number of list rows between consecutive pairs: pair p's mate-m list starts at
+ * ids_m + p * row_step * k (scores_m likewise) and its count is cnt_m[p * row_step]. row_step = 1 takes two separate
+ * arrays; row_step = 2 with ids2 = ids1 + k, scores2 = scores1 + k, cnt2 = cnt1 + 1 takes one interleaved batch
+ * (read 2p is mate 1, read 2p + 1 mate 2). The device form consumes drm_post_process_sw_{static,dynamic}_device's
+ * d_top_ids, d_top_scores and d_status unchanged. */
+typedef struct {
+    int32_t ref_len, min_tlen, max_tlen, unpaired_penalty;
+} drm_pair_params;
+typedef struct {
+    int32_t j1, j2, score, tlen, n_proper, status;
+} drm_pair_result;
+/* Host pointers; runs on the current device. out[npairs]. */
+int drm_pair_hits(const drm_pair_params *p, const uint64_t *ids1, const int32_t *scores1, const int32_t *cnt1,
+                  const uint64_t *ids2, const int32_t *scores2, const int32_t *cnt2, int64_t npairs, int32_t k,
+                  int64_t row_step, drm_pair_result *out);
+/* Device-buffer form, enqueued on `stream`. Stateless: no handle, the current device. */
+int drm_pair_hits_device(const drm_pair_params *p, const uint64_t *d_ids1, const int32_t *d_scores1,
+                         const int32_t *d_cnt1, const uint64_t *d_ids2, const int32_t *d_scores2,
+                         const int32_t *d_cnt2, int64_t npairs, int32_t k, int64_t row_step, drm_pair_result *d_out,
+                         void *stream);
+/* Host only: the SAM fields that relate the two lines of a pair. in[0] is mate 1, in[1] mate 2: mapped, reverse
+ * (the strand of a mapped mate), pos1 (1-based leftmost position) and ref_span = ref_end - ref_begin of its alignment
+ * record; the last three are ignored for an unmapped mate. proper != 0: the pairing chose a proper combination.
+ * flag = 0x1 | 0x40 (mate 1) or 0x80 (mate 2) | 0x4 self unmapped | 0x8 mate unmapped | 0x10 self mapped and reverse |
+ *        0x20 mate mapped and reverse | 0x2 iff proper and both mapped.
+ * Both mapped: pos = the read's own pos1, pnext = the mate's, has_rname = 1; L = max(pos1 + ref_span - 1) -
+ *   min(pos1) + 1 over the two; the mate with the smaller pos1 gets tlen = +L, the other -L, mate 1 gets +L when the
+ *   pos1 are equal. One mapped: both lines carry the mapped mate's position in pos and pnext, tlen = 0, has_rname = 1.
+ * None mapped: has_rname = 0 and pos = pnext = tlen = 0.
+ * DRM_ERR_ARG: a null pointer, or a mapped mate with pos1 < 1 or ref_span < 1. */
+typedef struct {
+    int32_t mapped, reverse;
+    int64_t pos1;
+    int32_t ref_span;
+} drm_sam_mate;
+typedef struct {
+    int32_t flag, has_rname;
+    int64_t pos, pnext, tlen;
+} drm_sam_mate_fields;
+int drm_sam_pair_fields(const drm_sam_mate in[2], int proper, drm_sam_mate_fields out[2]);
+
 /* ---------------------------------------------------------------- L2 rerank (the reference's live path)
  * post_process_l2_static (src/utils/post_processor.cpp:1023-1162, called at src/main.cpp:330) ->
  * find_sequences (static) -> Vectorizer::vectorize of the candidate windows -> batch_reranker(k = k_clusters)

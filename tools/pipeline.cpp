@@ -15,6 +15,10 @@
 // reference's pseudo POS / CIGAR in that SAM by the GPU alignment of every row (drm_sw_align); with
 // DRM_SAM_SCORING=match,mismatch,open,extend and / or DRM_SAM_FLANK=n beside it, by the affine-gap alignment over the
 // window widened by n genome bases on either side (drm_sw_align_affine).
+// DRM_MATES=<fastq of second mates> (with use_dynamic=1 use_streaming=1 DRM_SAM_CIGAR=1) maps read pairs: the two files
+// are interleaved, searched and reranked as one batch, drm_pair_hits chooses one hit per mate (DRM_PAIR_TLEN=min,max,
+// DRM_PAIR_PENALTY=n), only those are aligned, and the SAM carries two lines per pair with the pair flags, RNEXT,
+// PNEXT and TLEN (drm_sam_pair_fields).
 // Sequence inputs are embedded by the reference's GRU model on the GPU (drm_vectorize) when
 // DRM_ENCODER names it (.xml IR or .drmenc) or when the reference's models/ path exists in the working
 // directory (Config::Inference::MODEL_PATH); otherwise by the deterministic 3-mer stand-in. The rerank is
@@ -194,6 +198,45 @@ static bool affine_mode_from_env(size_t ref_len, AffineMode &mode)
     return true;
 }
 
+// DRM_MATES=<second mates> turns the paired mode on; DRM_PAIR_TLEN=min,max (default 0,1000) and DRM_PAIR_PENALTY=n
+// (default 17, bwa-mem's unpaired penalty) are read only then, as strictly as DRM_SAM_SCORING, and checked against
+// drm_pair_hits' ranges before any work.
+struct PairMode {
+    std::string mates;
+    drm_pair_params prm;
+};
+
+static bool pair_mode_from_env(size_t ref_len, PairMode &mode)
+{
+    const char *mates = std::getenv("DRM_MATES");
+    if (!mates)
+        return false;
+    if (!*mates)
+        throw drm::Error(DRM_ERR_ARG, "DRM_MATES is empty: it names the file of second mates");
+    if (ref_len < 1 || ref_len > ((size_t)1 << 20))
+        throw drm::Error(DRM_ERR_UNSUPPORTED, "DRM_MATES: ref_len " + std::to_string(ref_len) + " outside [1, 2^20]");
+    mode.mates = mates;
+    mode.prm = drm_pair_params{(int32_t)ref_len, 0, 1000, 17};
+    if (const char *tl = std::getenv("DRM_PAIR_TLEN")) {
+        const std::string s(tl);
+        const size_t c = s.find(',');
+        long lo = 0, hi = 0;
+        if (c == std::string::npos || !parse_int(s.substr(0, c), lo) || !parse_int(s.substr(c + 1), hi))
+            throw drm::Error(DRM_ERR_ARG, "DRM_PAIR_TLEN must be min,max (two non-negative integers): \"" + s + "\"");
+        if (lo > hi || hi > (1L << 30))
+            throw drm::Error(DRM_ERR_ARG, "DRM_PAIR_TLEN must be min,max with 0 <= min <= max <= 2^30: \"" + s + "\"");
+        mode.prm.min_tlen = (int32_t)lo;
+        mode.prm.max_tlen = (int32_t)hi;
+    }
+    if (const char *pe = std::getenv("DRM_PAIR_PENALTY")) {
+        long x = 0;
+        if (!parse_int(pe, x) || x > (1L << 20))
+            throw drm::Error(DRM_ERR_ARG, std::string("DRM_PAIR_PENALTY must be an integer in [0, 2^20]: \"") + pe + "\"");
+        mode.prm.unpaired_penalty = (int32_t)x;
+    }
+    return true;
+}
+
 int main(int argc, char *argv[])
 {
     if (argc < 4 || argc > 10) {
@@ -237,6 +280,18 @@ int main(int argc, char *argv[])
         AffineMode affine_mode{};
         const bool cigar_env = std::getenv("DRM_SAM_CIGAR") && std::atoi(std::getenv("DRM_SAM_CIGAR")) != 0;
         const AffineMode *affine = cigar_env && affine_mode_from_env(ref_len, affine_mode) ? &affine_mode : nullptr;
+        PairMode pair_mode{};
+        const bool paired = pair_mode_from_env(ref_len, pair_mode);
+        if (paired) {
+            if (!use_dynamic || !use_streaming)
+                throw drm::Error(DRM_ERR_ARG, "DRM_MATES needs use_dynamic=1 and use_streaming=1: pairs are written to the "
+                                              "streamed SAM");
+            if (!cigar_env)
+                throw drm::Error(DRM_ERR_ARG, "DRM_MATES needs DRM_SAM_CIGAR=1: the pair fields come from real alignments");
+            if (std::filesystem::path(query_file).extension() == ".npy" ||
+                std::filesystem::path(pair_mode.mates).extension() == ".npy")
+                throw drm::Error(DRM_ERR_ARG, "DRM_MATES needs sequence files for both mates, not .npy embeddings");
+        }
         // devices: DRM_DEVICES=0,1,... fans the batch out over several GPUs (contiguous query shards,
         // replicated index); DRM_DEVICE=i picks one (default 0)
         std::vector<int> devices;
@@ -254,6 +309,8 @@ int main(int argc, char *argv[])
         if (devices.empty())
             devices.push_back(std::getenv("DRM_DEVICE") ? std::atoi(std::getenv("DRM_DEVICE")) : 0);
         const int device = devices[0];
+        if (paired && devices.size() != 1)
+            throw drm::Error(DRM_ERR_UNSUPPORTED, "DRM_MATES runs on one device (DRM_DEVICE), not on DRM_DEVICES");
 
         // ---- data loading
         std::vector<float> emb;
@@ -277,6 +334,30 @@ int main(int argc, char *argv[])
             if (qseqs.empty()) {
                 std::cerr << "No query_sequences found in input file!" << std::endl;
                 return 1;
+            }
+            if (paired) { // mate 1 of pair i becomes query 2i, mate 2 query 2i + 1
+                std::vector<std::string> seqs2, ids2;
+                drm::read_file(pair_mode.mates, seqs2, ids2);
+                const size_t n1 = qseqs.size(), n2 = seqs2.size();
+                auto name = [](const std::vector<std::string> &ids, size_t i) { return i < ids.size() ? ids[i] : std::string(); };
+                for (size_t i = 0; i < std::min(n1, n2); ++i)
+                    if (name(qids, i) != name(ids2, i))
+                        throw drm::Error(DRM_ERR_FORMAT, "DRM_MATES: record " + std::to_string(i) + " is named \"" +
+                                                             name(qids, i) + "\" in " + query_file + " and \"" +
+                                                             name(ids2, i) + "\" in " + pair_mode.mates);
+                if (n1 != n2)
+                    throw drm::Error(DRM_ERR_FORMAT, "DRM_MATES: " + query_file + " has " + std::to_string(n1) +
+                                                         " records and " + pair_mode.mates + " has " + std::to_string(n2) +
+                                                         ": record " + std::to_string(std::min(n1, n2)) + " has no mate");
+                std::vector<std::string> seqs(2 * n1), ids(2 * n1);
+                for (size_t i = 0; i < n1; ++i) {
+                    seqs[2 * i] = std::move(qseqs[i]);
+                    seqs[2 * i + 1] = std::move(seqs2[i]);
+                    ids[2 * i] = ids[2 * i + 1] = name(qids, i);
+                }
+                qseqs.swap(seqs);
+                qids.swap(ids);
+                std::cout << "[MAIN] Paired mode: " << n1 << " pairs, mates from " << pair_mode.mates << std::endl;
             }
             nq = qseqs.size();
         }
@@ -418,9 +499,10 @@ int main(int argc, char *argv[])
         // reranker meant to write: the L2 rows of every query, and none for a query whose
         // candidate range runs past the clipped expansion stream (the reference reads out of bounds there).
         const bool stream_sam = use_streaming && dyn;
-        const bool sam_from_search = stream_sam && stride == 1;
+        // DRM_MATES: pairing needs scores, so the SW rerank runs whatever the stride
+        const bool sam_from_search = stream_sam && stride == 1 && !paired;
         const bool l2_rows = std::getenv("DRM_SAM_L2_ROWS") && std::atoi(std::getenv("DRM_SAM_L2_ROWS")) != 0;
-        const bool sam_header_only = stream_sam && stride > 1 && !l2_rows;
+        const bool sam_header_only = stream_sam && stride > 1 && !l2_rows && !paired;
         // DRM_SAM_CIGAR=1: every SAM row gets its real POS / CIGAR / AS / NM from a GPU
         // alignment of the block's rows (drm_sw_align) before the host thread formats the block. Unset: no
         // alignment is launched and the file is the reference's.
@@ -439,10 +521,11 @@ int main(int argc, char *argv[])
                 block = std::max<size_t>(1, std::min<size_t>(block, ((size_t)1 << 22) / std::max<size_t>(rows_per_query, 1)));
             return block;
         };
-        const bool sam_l2 = stream_sam && stride > 1 && l2_rows && rt && !is_npy && !drm::encoder_model_path().empty();
+        const bool sam_l2 = stream_sam && stride > 1 && l2_rows && rt && !is_npy && !drm::encoder_model_path().empty() &&
+                            !paired;
         if (stream_sam && (size_t)k > (size_t)k_clusters * 2 * stride) // post_processor.cpp:769-772
             throw drm::Error(DRM_ERR_K, "Final k too large. Ensure k < k_clusters * 2 * stride to have enough candidates.");
-        if (stream_sam && stride > 1 && l2_rows && !sam_l2)
+        if (stream_sam && stride > 1 && l2_rows && !sam_l2 && !paired)
             std::cout << "[MAIN] stride > 1 without the GRU model on one device: SAM rows from the SW rerank (the "
                          "reference reranks them by L2 here)"
                       << std::endl;
@@ -513,6 +596,69 @@ int main(int argc, char *argv[])
                                          cnt.data() + lo, (size_t)k, sam_cigar ? &av : nullptr);
                 }
             }
+        } else if (paired) {
+            // per block of pairs: search + SW rerank of its 2m interleaved reads, drm_pair_hits over the block's
+            // lists (row_step 2), the alignment of only the chosen row of every read, and the two lines per pair from
+            // the writer thread while the GPU works on the next block. DRM_SAM_BLOCK counts pairs here; the file does
+            // not depend on it.
+            std::cout << "[MAIN] Using STREAMING output to SAM file: " << sam_file << " (paired)" << std::endl;
+            std::filesystem::create_directories(out_dir);
+            const size_t npairs = nq / 2, block = sam_block(2);
+            std::thread writer;
+            std::string werr;
+            for (size_t p0 = 0; p0 < npairs && rc == DRM_OK; p0 += block) {
+                const size_t mp = std::min(block, npairs - p0), lo = 2 * p0, m = 2 * mp;
+                drm_search_stats bs{};
+                rc = run(lo, m, &bs);
+                st.nq += bs.nq;
+                st.ndis += bs.ndis;
+                st.nhops += bs.nhops;
+                st.kernel_ms += bs.kernel_ms;
+                auto ids = std::make_shared<std::vector<uint64_t>>(m, 0);
+                auto cnt = std::make_shared<std::vector<int32_t>>(m, 0);
+                auto proper = std::make_shared<std::vector<int32_t>>(mp, 0);
+                auto ba = std::make_shared<BlockAlignments>();
+                if (rc == DRM_OK) {
+                    try {
+                        std::vector<drm_pair_result> res(mp);
+                        check(drm_set_device(device));
+                        const size_t at = lo * (size_t)k;
+                        check(drm_pair_hits(&pair_mode.prm, sw_ids.p + at, sw_scores.p + at, status.p + lo,
+                                            sw_ids.p + at + k, sw_scores.p + at + k, status.p + lo + 1, (int64_t)mp, k, 2,
+                                            res.data()));
+                        for (size_t p = 0; p < mp; ++p) {
+                            const int32_t j[2] = {res[p].j1, res[p].j2};
+                            for (size_t t = 0; t < 2; ++t)
+                                if (j[t] >= 0) {
+                                    (*ids)[2 * p + t] = sw_ids.p[(lo + 2 * p + t) * (size_t)k + (size_t)j[t]];
+                                    (*cnt)[2 * p + t] = 1;
+                                }
+                            (*proper)[p] = res[p].status == 0;
+                        }
+                        ba->align(art, ids->data(), cnt->data(), m, 1, qbuf.p + lo * qs, ql.p + lo, (int32_t)qs,
+                                  (int32_t)ref_len, affine);
+                    } catch (...) {
+                        if (writer.joinable())
+                            writer.join();
+                        throw;
+                    }
+                }
+                if (writer.joinable())
+                    writer.join();
+                if (rc == DRM_OK && werr.empty())
+                    writer = std::thread([&, lo, mp, ids, cnt, proper, ba] {
+                        try {
+                            drm::write_sam_pairs(sam_file, lo == 0, "ref", ref_len, qseqs, qids, lo, mp, ids->data(),
+                                                 cnt->data(), proper->data(), ba->view());
+                        } catch (const std::exception &e) {
+                            werr = e.what();
+                        }
+                    });
+            }
+            if (writer.joinable())
+                writer.join();
+            if (rc == DRM_OK && !werr.empty())
+                throw drm::Error(DRM_ERR_IO, werr);
         } else if (stream_sam) {
             // post_process_*_dynamic_streaming + write_sam_streaming (src/main.cpp:316-319,
             // src/utils/utils.cpp:409-503): the SAM lines of each block are written by a host thread while the
