@@ -12,6 +12,8 @@ from .rerank import (WindowTable, calc_sw_score, calc_sw_scores, post_process_sw
                      SW_ALIGNMENT_DTYPE, sw_align_affine_arrays, sw_align_region, sam_cigar_region)
 
 from .pairing import PAIR_RESULT_DTYPE, pair_hits, pair_hits_device, sam_pair_fields  # noqa: F401  (paired-end reads)
+from .pairing import (RESCUE_RESULT_DTYPE, mate_rescue, mate_rescue_device, mate_rescue_region,  # noqa: F401
+                      mate_rescue_window, pair_rescue_choose)  # (mate rescue)
 
 __version__ = "0.4.0"
 from .executor import Comm, MultiIndex, search_rerank  # noqa: F401  (batch executor, multi-GPU, RCCL gather)

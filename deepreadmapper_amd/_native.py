@@ -49,6 +49,8 @@ EXPORTS = [
     "drm_exact_search", "drm_exact_search_device", "drm_exact_search_l2", "drm_exact_search_l2_device",
     "drm_flat_exact_search", "drm_exact_set_slice_rows", "drm_exact_query_tile",
     "drm_pair_hits", "drm_pair_hits_device", "drm_sam_pair_fields",
+    "drm_mate_rescue", "drm_mate_rescue_device", "drm_mate_rescue_region", "drm_mate_rescue_window",
+    "drm_pair_rescue_choose",
 ]
 
 
@@ -206,6 +208,12 @@ def lib():
         "drm_pair_hits": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, i32, i64, vp]),
         "drm_pair_hits_device": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, i32, i64, vp, vp]),
         "drm_sam_pair_fields": (C.c_int, [vp, C.c_int, vp]),
+        "drm_mate_rescue": (C.c_int, [vp, vp, vp, vp, vp, i64, vp, vp, i32, i64, vp]),
+        "drm_mate_rescue_device": (C.c_int, [vp, vp, vp, vp, vp, i64, vp, vp, i32, i64, vp, vp]),
+        "drm_mate_rescue_region": (C.c_int, [vp, i64, C.c_uint64, C.POINTER(i64), C.POINTER(i32), C.POINTER(i32)]),
+        "drm_mate_rescue_window": (C.c_int, [vp, i32, i64, C.POINTER(C.c_uint64)]),
+        "drm_pair_rescue_choose": (C.c_int, [vp, i32, i32, C.c_uint64, C.c_uint64, vp, vp, i32, i64, i32, i32, vp,
+                                              C.POINTER(C.c_uint64)]),
         "drm_exact_search": (C.c_int, [vp, vp, i64, i32, i32, vp, vp, C.POINTER(C.c_double)]),
         "drm_exact_search_device": (C.c_int, [vp, vp, i64, i32, vp, vp, vp]),
         "drm_exact_search_l2": (C.c_int, [vp, i64, i32, vp, i64, i32, vp, vp, C.POINTER(C.c_double)]),

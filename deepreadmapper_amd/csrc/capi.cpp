@@ -1767,10 +1767,9 @@ int drm_sw_align(drm_refs *refs, const uint64_t *window_ids, const int64_t *pair
 }
 
 // ---------------------------------------------------------------------- affine-gap alignment (sw_align_affine.hip)
-static drm::AffineAlignArgs make_affine_args(const drm_refs *refs, const drm_sw_scoring *sc, int32_t flank)
+// drm_sw_scoring's accepted ranges (drm_sw_align_affine, drm_mate_rescue)
+static void check_scoring(const drm_sw_scoring *sc)
 {
-    if (!refs || !sc)
-        throw Error(DRM_ERR_ARG, "null refs / scoring");
     auto range = [](const char *name, int32_t v, int32_t lo, int32_t hi) {
         if (v < lo || v > hi)
             throw Error(DRM_ERR_ARG, std::string("scoring: ") + name + " " + std::to_string(v) + " outside [" +
@@ -1780,6 +1779,13 @@ static drm::AffineAlignArgs make_affine_args(const drm_refs *refs, const drm_sw_
     range("mismatch", sc->mismatch, 1, 63);
     range("gap_open", sc->gap_open, 0, 63);
     range("gap_extend", sc->gap_extend, 1, 63);
+}
+
+static drm::AffineAlignArgs make_affine_args(const drm_refs *refs, const drm_sw_scoring *sc, int32_t flank)
+{
+    if (!refs || !sc)
+        throw Error(DRM_ERR_ARG, "null refs / scoring");
+    check_scoring(sc);
     if (flank < 0)
         throw Error(DRM_ERR_ARG, "negative flank");
     if (flank > 0 && !refs->dev.genome)
@@ -1932,6 +1938,102 @@ int drm_pair_hits(const drm_pair_params *p, const uint64_t *ids1, const int32_t 
         a.cnt2 = dc2.p;
         a.out = dout.p;
         drm::launch_pair_hits(a, nullptr);
+        DRM_HIP_CHECK(hipDeviceSynchronize());
+        dout.download(out);
+    });
+}
+
+// ---------------------------------------------------------------------- mate rescue (mate_rescue.hip)
+static drm::RescueArgs make_rescue_args(const drm_refs *refs, const drm_sw_scoring *sc, const drm_pair_params *p,
+                                        const uint64_t *anchors, const int64_t *tq, int64_t ntasks, const uint8_t *q,
+                                        const int32_t *ql, int32_t q_stride, int64_t nq, drm_rescue_result *out)
+{
+    if (!refs || !sc || !p)
+        throw Error(DRM_ERR_ARG, "null refs / scoring / pair parameters");
+    if (!refs->dev.genome)
+        throw Error(DRM_ERR_ARG, "mate rescue needs a genome handle: a window table holds nothing between its rows");
+    check_scoring(sc);
+    drm::RescueArgs a{};
+    drm::check_rescue_params(p, a.dlo, a.dhi);
+    if (p->ref_len != refs->dev.ref_len)
+        throw Error(DRM_ERR_ARG, "the pair parameters' ref_len " + std::to_string(p->ref_len) + " is not the handle's " +
+                                     std::to_string(refs->dev.ref_len));
+    if (ntasks < 0 || nq < 0 || q_stride < 0)
+        throw Error(DRM_ERR_ARG, "negative ntasks / nq / q_stride");
+    a.genome = refs->dev.genome;
+    a.glen = refs->dev.glen;
+    a.ref_len = p->ref_len;
+    a.match = sc->match;
+    a.mismatch = sc->mismatch;
+    a.gap_open = sc->gap_open;
+    a.gap_extend = sc->gap_extend;
+    a.anchor_ids = anchors;
+    a.task_query = tq;
+    a.ntasks = ntasks;
+    a.queries = q;
+    a.q_len = ql;
+    a.q_stride = q_stride;
+    a.nq = nq;
+    a.out = out;
+    return a;
+}
+
+int drm_mate_rescue_device(drm_refs *refs, const drm_sw_scoring *scoring, const drm_pair_params *p,
+                           const uint64_t *d_anchor_ids, const int64_t *d_task_query, int64_t ntasks,
+                           const uint8_t *d_queries, const int32_t *d_q_len, int32_t q_stride, int64_t nq,
+                           drm_rescue_result *d_out, void *stream)
+{
+    return guarded([&] {
+        const drm::RescueArgs a = make_rescue_args(refs, scoring, p, d_anchor_ids, d_task_query, ntasks, d_queries,
+                                                   d_q_len, q_stride, nq, d_out);
+        if (ntasks == 0)
+            return;
+        if (!d_anchor_ids || !d_task_query || !d_out || (nq > 0 && (!d_queries || !d_q_len)))
+            throw Error(DRM_ERR_ARG, "null argument");
+        DRM_HIP_CHECK(hipSetDevice(refs->dev.device));
+        // max query length bounded by the row stride of the query buffer
+        drm::launch_mate_rescue(refs->dev.device, a, q_stride, (hipStream_t)stream);
+    });
+}
+
+int drm_mate_rescue(drm_refs *refs, const drm_sw_scoring *scoring, const drm_pair_params *p,
+                    const uint64_t *anchor_ids, const int64_t *task_query, int64_t ntasks, const uint8_t *queries,
+                    const int32_t *q_len, int32_t q_stride, int64_t nq, drm_rescue_result *out)
+{
+    return guarded([&] {
+        drm::RescueArgs a = make_rescue_args(refs, scoring, p, nullptr, nullptr, ntasks, nullptr, nullptr, q_stride,
+                                             nq, nullptr);
+        if (ntasks == 0)
+            return;
+        if (!anchor_ids || !task_query || !out || (nq > 0 && (!queries || !q_len)))
+            throw Error(DRM_ERR_ARG, "null argument");
+        int max_q = 0;
+        for (int64_t i = 0; i < nq; ++i) {
+            if (q_len[i] < 0 || q_len[i] > q_stride)
+                throw Error(DRM_ERR_ARG, "query length outside [0, q_stride]");
+            max_q = std::max(max_q, q_len[i]);
+        }
+        for (int64_t t = 0; t < ntasks; ++t)
+            if (task_query[t] < 0 || task_query[t] >= nq)
+                throw Error(DRM_ERR_ARG, "task " + std::to_string(t) + " names query " + std::to_string(task_query[t]) +
+                                             " outside [0, " + std::to_string(nq) + ")");
+        DRM_HIP_CHECK(hipSetDevice(refs->dev.device));
+        DevBuf<uint64_t> di((size_t)ntasks);
+        DevBuf<int64_t> dt((size_t)ntasks);
+        DevBuf<uint8_t> dq((size_t)nq * (size_t)q_stride);
+        DevBuf<int32_t> dl((size_t)nq);
+        DevBuf<drm_rescue_result> dout((size_t)ntasks);
+        di.upload(anchor_ids);
+        dt.upload(task_query);
+        if (dq.n)
+            dq.upload(queries);
+        dl.upload(q_len);
+        a.anchor_ids = di.p;
+        a.task_query = dt.p;
+        a.queries = dq.p;
+        a.q_len = dl.p;
+        a.out = dout.p;
+        drm::launch_mate_rescue(refs->dev.device, a, max_q, nullptr);
         DRM_HIP_CHECK(hipDeviceSynchronize());
         dout.download(out);
     });

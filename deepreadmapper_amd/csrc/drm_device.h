@@ -331,6 +331,26 @@ struct PairArgs {
 };
 void launch_pair_hits(const PairArgs &a, hipStream_t stream);
 
+// Mate rescue (mate_rescue.hip; drm_mate_rescue): one wave per task, the score-only Gotoh scan of
+// query task_query[t] over rescue_region(anchor_ids[t]) of the genome, at most kRescueMaxRows rows. Throws
+// Error(DRM_ERR_UNSUPPORTED) for a query longer than kAlignMaxLen or a region cap beyond kRescueMaxRows.
+struct RescueArgs {
+    const uint8_t *genome;
+    int64_t glen;
+    int32_t ref_len;
+    int64_t dlo, dhi;
+    int32_t match, mismatch, gap_open, gap_extend; // the last three are penalties (drm_sw_scoring)
+    const uint64_t *anchor_ids; // [ntasks]
+    const int64_t *task_query;  // [ntasks] index into queries
+    int64_t ntasks;
+    const uint8_t *queries; // [nq][q_stride]
+    const int32_t *q_len;
+    int32_t q_stride;
+    int64_t nq;
+    drm_rescue_result *out; // [ntasks]
+};
+void launch_mate_rescue(int device, const RescueArgs &a, int max_qlen, hipStream_t stream);
+
 // L2 rerank (post_process_l2_static -> batch_reranker, src/utils/post_processor.cpp:1023-1162,
 // src/utils/reranker.cpp:98-195): distances from the window embedding table, libstdc++ partial_sort
 struct L2Args {

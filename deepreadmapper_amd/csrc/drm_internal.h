@@ -171,6 +171,46 @@ void write_sam_pairs(const std::string &path, bool header, const std::string &re
                      size_t q0, size_t npairs, const uint64_t *ids, const int32_t *counts, const int32_t *proper,
                      const SamAlignments &aln);
 
+// Mate rescue (include/drm_hip.h, drm_mate_rescue): the region of one anchor id, the one statement of the rule that
+// the host entry points (formats.cpp) and the kernel (mate_rescue.hip) both compile. dlo / dhi are
+// max(0, min_tlen - ref_len) and max_tlen - ref_len.
+#if defined(__HIPCC__)
+#define DRM_HOST_DEVICE __host__ __device__
+#else
+#define DRM_HOST_DEVICE
+#endif
+constexpr int kRescueMaxRows = 2048; // longest region: 11 bits of row in the kernel's best-cell key
+struct RescueRegion {
+    int64_t start;
+    int32_t len, reverse;
+};
+DRM_HOST_DEVICE inline RescueRegion rescue_region(uint64_t w, int64_t glen, int32_t ref_len, int64_t dlo, int64_t dhi)
+{
+    RescueRegion r{0, 0, (int32_t)(1u - (uint32_t)(w & 1u))};
+    const uint64_t a = w >> 1;
+    if (dhi < dlo || glen < 0 || a + (uint64_t)ref_len > (uint64_t)glen)
+        return r;
+    const int64_t pos = (int64_t)a; // <= glen from here on: nothing below overflows
+    int64_t s, e;
+    if (r.reverse) {
+        s = pos + dlo;
+        e = pos + dhi + ref_len;
+        s = s < glen ? s : glen;
+    } else {
+        s = pos - dhi;
+        e = pos - dlo + ref_len;
+        s = s > 0 ? s : 0;
+    }
+    e = e < glen ? e : glen;
+    if (e <= s)
+        return r;
+    r.start = s;
+    r.len = (int32_t)(e - s);
+    return r;
+}
+// drm_pair_hits' ranges of ref_len and the template lengths, and the rescue's row cap; returns dlo / dhi
+void check_rescue_params(const drm_pair_params *p, int64_t &dlo, int64_t &dhi);
+
 void build_hnswpq(const float *x, int64_t n, int d, int M_pq, int nbits, int M_hnsw, int efc, double sample_rate,
                   int nthreads, uint64_t seed, const std::string &path);
 // Shared by the CPU builder (builder.cpp) and the GPU builder (builder_gpu.hip):

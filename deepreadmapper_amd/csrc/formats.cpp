@@ -533,6 +533,143 @@ extern "C" int drm_sam_pair_fields(const drm_sam_mate in[2], int proper, drm_sam
     }
 }
 
+// ----------------------------------------------------------------------- mate rescue: the host-only parts
+void drm::check_rescue_params(const drm_pair_params *p, int64_t &dlo, int64_t &dhi)
+{
+    if (!p)
+        throw Error(DRM_ERR_ARG, "null pair parameters");
+    if (p->ref_len < 1 || p->ref_len > (1 << 20))
+        throw Error(DRM_ERR_ARG, "ref_len " + std::to_string(p->ref_len) + " outside [1, 2^20]");
+    if (p->min_tlen < 0 || p->min_tlen > p->max_tlen || p->max_tlen > (1 << 30))
+        throw Error(DRM_ERR_ARG, "template lengths [" + std::to_string(p->min_tlen) + ", " +
+                                     std::to_string(p->max_tlen) + "] must satisfy 0 <= min <= max <= 2^30");
+    dlo = std::max<int64_t>((int64_t)p->min_tlen - p->ref_len, 0);
+    dhi = (int64_t)p->max_tlen - p->ref_len;
+    if (dhi - dlo + p->ref_len > kRescueMaxRows)
+        throw Error(DRM_ERR_UNSUPPORTED, "template lengths [" + std::to_string(p->min_tlen) + ", " +
+                                             std::to_string(p->max_tlen) + "] at ref_len " +
+                                             std::to_string(p->ref_len) + " give a rescue region of " +
+                                             std::to_string(dhi - dlo + p->ref_len) + " > 2048 rows");
+}
+
+static uint64_t rescue_window(const drm_rescue_result &r, int32_t ref_len, int64_t glen)
+{
+    using drm::Error;
+    if (r.status != 0)
+        throw Error(DRM_ERR_ARG, "the rescue record holds no hit (status " + std::to_string(r.status) + ")");
+    if (ref_len < 1 || glen < ref_len)
+        throw Error(DRM_ERR_ARG, "ref_len " + std::to_string(ref_len) + " and genome length " + std::to_string(glen) +
+                                     " leave no window");
+    if (r.region_len < 1 || r.ref_end < 1 || r.ref_end > r.region_len || r.region_start < 0 ||
+        r.region_start > glen - r.region_len)
+        throw Error(DRM_ERR_ARG, "the rescue record's region or end row does not lie in a genome of " +
+                                     std::to_string(glen) + " bases");
+    int64_t p =r.reverse ? r.region_start + r.region_len - r.ref_end : r.region_start + r.ref_end - ref_len;
+    p = std::min(std::max<int64_t>(p, 0), glen - ref_len);
+    return 2 * (uint64_t)p + (r.reverse ? 1u : 0u);
+}
+
+static void pair_rescue_choose(const drm_pair_result &pair, int32_t s1, int32_t s2, uint64_t anchor1, uint64_t anchor2,
+                               const drm_rescue_result *rA, const drm_rescue_result *rB, int32_t ref_len, int64_t glen,
+                               int32_t penalty, int32_t min_score, drm_pair_result &out, uint64_t &rescued_id)
+{
+    using drm::Error;
+    if (pair.status < 0 || pair.status > 4)
+        throw Error(DRM_ERR_ARG, "pair status " + std::to_string(pair.status) + " outside [0, 4]");
+    out = pair;
+    rescued_id = 0;
+    const bool validA = rA && rA->status == 0 && rA->score >= min_score;
+    const bool validB = rB && rB->status == 0 && rB->score >= min_score;
+    const int64_t sumA = validA ? (int64_t)s1 + rA->score : 0, sumB = validB ? (int64_t)rB->score + s2 : 0;
+    bool useA = false, useB = false;
+    if (pair.status == 1) {
+        const int64_t need = (int64_t)s1 + s2 - penalty;
+        const bool qa = validA && sumA >= need, qb = validB && sumB >= need;
+        useA = qa && (!qb || sumA >= sumB);
+        useB = qb && !useA;
+    } else if (pair.status == 2) {
+        useA = validA;
+    } else if (pair.status == 3) {
+        useB = validB;
+    }
+    if (!useA && !useB)
+        return;
+    const drm_rescue_result &r = useA ? *rA : *rB;
+    const uint64_t anchor = useA ? anchor1 : anchor2;
+    const uint64_t wr = rescue_window(r, ref_len, glen);
+    // the rescued hit lies on the strand opposite to the anchor's: the forward one of the two is f
+    const int64_t pa = (int64_t)(anchor >> 1), pr = (int64_t)(wr >> 1);
+    const int64_t tlen = (anchor & 1u) ? pa + ref_len - pr : pr + ref_len - pa;
+    out.status = useA ? 5 : 6;
+    (useA ? out.j2 : out.j1) = -1;
+    out.score = (int32_t)(useA ? sumA : sumB);
+    out.tlen = (int32_t)tlen;
+    rescued_id = wr;
+}
+
+extern "C" int drm_mate_rescue_region(const drm_pair_params *p, int64_t glen, uint64_t anchor_id, int64_t *start,
+                                      int32_t *len, int32_t *reverse)
+{
+    try {
+        if (!p || !start || !len || !reverse)
+            throw drm::Error(DRM_ERR_ARG, "null argument");
+        if (glen < 0)
+            throw drm::Error(DRM_ERR_ARG, "negative genome length");
+        int64_t dlo = 0, dhi = 0;
+        drm::check_rescue_params(p, dlo, dhi);
+        const drm::RescueRegion r = drm::rescue_region(anchor_id, glen, p->ref_len, dlo, dhi);
+        *start = r.start;
+        *len = r.len;
+        *reverse = r.reverse;
+        return DRM_OK;
+    } catch (const drm::Error &e) {
+        drm::set_last_error(e.what());
+        return e.code;
+    } catch (const std::exception &e) {
+        drm::set_last_error(e.what());
+        return DRM_ERR_ARG;
+    }
+}
+
+extern "C" int drm_mate_rescue_window(const drm_rescue_result *r, int32_t ref_len, int64_t glen, uint64_t *window_id)
+{
+    try {
+        if (!r || !window_id)
+            throw drm::Error(DRM_ERR_ARG, "null argument");
+        *window_id = rescue_window(*r, ref_len, glen);
+        return DRM_OK;
+    } catch (const drm::Error &e) {
+        drm::set_last_error(e.what());
+        return e.code;
+    } catch (const std::exception &e) {
+        drm::set_last_error(e.what());
+        return DRM_ERR_ARG;
+    }
+}
+
+extern "C" int drm_pair_rescue_choose(const drm_pair_result *pair, int32_t s1, int32_t s2, uint64_t anchor1,
+                                      uint64_t anchor2, const drm_rescue_result *rA, const drm_rescue_result *rB,
+                                      int32_t ref_len, int64_t glen, int32_t unpaired_penalty, int32_t min_score,
+                                      drm_pair_result *out, uint64_t *rescued_id)
+{
+    try {
+        if (!pair || !out || !rescued_id)
+            throw drm::Error(DRM_ERR_ARG, "null argument");
+        drm_pair_result o{};
+        uint64_t w = 0;
+        pair_rescue_choose(*pair, s1, s2, anchor1, anchor2, rA, rB, ref_len, glen, unpaired_penalty, min_score, o, w);
+        *out = o;
+        *rescued_id = w;
+        return DRM_OK;
+    } catch (const drm::Error &e) {
+        drm::set_last_error(e.what());
+        return e.code;
+    } catch (const std::exception &e) {
+        drm::set_last_error(e.what());
+        return DRM_ERR_ARG;
+    }
+}
+
 void drm::write_sam_pairs(const std::string &path, bool header, const std::string &ref_name, size_t ref_len,
                           const std::vector<std::string> &query_seqs, const std::vector<std::string> &query_ids,
                           size_t q0, size_t npairs, const uint64_t *ids, const int32_t *counts, const int32_t *proper,

@@ -1,6 +1,8 @@
 """Paired-end reads: which hit of mate 1 and which hit of mate 2 belong to one fragment (drm_pair_hits, the HIP kernel
-of csrc/pair_hits.hip), and the SAM fields that relate a pair's two lines (drm_sam_pair_fields). The definitions are
-in include/drm_hip.h."""
+of csrc/pair_hits.hip), the SAM fields that relate a pair's two lines (drm_sam_pair_fields), and the rescue of a mate
+the search lost: its score-only alignment over the insert window of its mate's hit (drm_mate_rescue, the HIP kernel
+of csrc/mate_rescue.hip) and the decision that follows (drm_pair_rescue_choose). The definitions are in
+include/drm_hip.h."""
 import ctypes as C
 
 import numpy as np
@@ -81,3 +83,92 @@ def sam_pair_fields(mate1, mate2, proper):
     out = np.zeros(2, dtype=SAM_MATE_FIELDS_DTYPE)
     check(lib().drm_sam_pair_fields(ptr(m), int(bool(proper)), ptr(out)))
     return tuple({f: int(out[f][i]) for f in SAM_MATE_FIELDS_DTYPE.names} for i in range(2))
+
+
+# ------------------------------------------------------------------------------------------- mate rescue
+# drm_rescue_result (include/drm_hip.h)
+RESCUE_RESULT_DTYPE = np.dtype([("region_start", np.int64)] +
+                               [(f, np.int32) for f in ("region_len", "reverse", "score", "ref_end", "q_end", "status")])
+RESCUE_SCORING = (1, 1, 0, 1)  # the rerank's scoring: what makes a rescued score comparable with a reranked one
+
+
+def _scoring(scoring):
+    s = np.array([int(x) for x in scoring], dtype=np.int32)
+    if s.shape != (4,):
+        raise ValueError("scoring is (match, mismatch, gap_open, gap_extend)")
+    return s
+
+
+def mate_rescue(table, anchor_ids, task_query, query_seqs, min_tlen=0, max_tlen=1000, scoring=RESCUE_SCORING,
+                ref_len=None):
+    """drm_mate_rescue on host arrays: task t aligns, score only, query task_query[t] of query_seqs (a list, or
+    pack_queries' (buffer, lengths)) against the insert window of the hit anchor_ids[t] on a GenomeTable. ref_len
+    defaults to the table's. Returns a structured array (RESCUE_RESULT_DTYPE), one record per task."""
+    from .rerank import pack_queries
+    wid = np.ascontiguousarray(anchor_ids, dtype=np.uint64)
+    tq = np.ascontiguousarray(task_query, dtype=np.int64)
+    if wid.shape != tq.shape or wid.ndim != 1:
+        raise ValueError("anchor_ids and task_query must be 1-d arrays of one length")
+    qbuf, qlen = query_seqs if isinstance(query_seqs, tuple) else pack_queries(query_seqs)
+    out = np.zeros(len(wid), dtype=RESCUE_RESULT_DTYPE)
+    prm = pair_params(table.ref_len if ref_len is None else ref_len, min_tlen, max_tlen, 0)
+    check(lib().drm_mate_rescue(table.handle, ptr(_scoring(scoring)), ptr(prm), ptr(wid), ptr(tq), len(wid),
+                                ptr(qbuf), ptr(qlen), qbuf.shape[1], len(qlen), ptr(out)))
+    return out
+
+
+def mate_rescue_device(table, d_anchor_ids, d_task_query, ntasks, d_queries, d_q_len, q_stride, nq, min_tlen=0,
+                       max_tlen=1000, scoring=RESCUE_SCORING, d_out=None, stream=None):
+    """drm_mate_rescue_device: the same on device memory, enqueued on `stream`. Each d_* argument is a DeviceBuffer or
+    a raw device address. Returns the DeviceBuffer of ntasks records (d_out, or a new one); synchronise the stream
+    before downloading it."""
+    from .device import DeviceBuffer
+
+    def addr(b):
+        return C.c_void_p(b.ptr if hasattr(b, "ptr") else int(b))
+    if d_out is None:
+        d_out = DeviceBuffer((int(ntasks),), RESCUE_RESULT_DTYPE)
+    prm = pair_params(table.ref_len, min_tlen, max_tlen, 0)
+    check(lib().drm_mate_rescue_device(table.handle, ptr(_scoring(scoring)), ptr(prm), addr(d_anchor_ids),
+                                       addr(d_task_query), int(ntasks), addr(d_queries), addr(d_q_len), int(q_stride),
+                                       int(nq), addr(d_out), stream.handle if stream is not None else None))
+    return d_out
+
+
+def mate_rescue_region(glen, ref_len, anchor_id, min_tlen=0, max_tlen=1000):
+    """(start, length, reverse) of an anchor's rescue region on a genome of glen bases (drm_mate_rescue_region): the
+    bytes genome[start : start + length], reverse-complemented when reverse; length 0 for an empty region."""
+    start, n, rev = C.c_int64(0), C.c_int32(0), C.c_int32(0)
+    prm = pair_params(ref_len, min_tlen, max_tlen, 0)
+    check(lib().drm_mate_rescue_region(ptr(prm), int(glen), int(anchor_id), C.byref(start), C.byref(n), C.byref(rev)))
+    return start.value, n.value, rev.value
+
+
+def _rescue_record(r):
+    rec = np.zeros(1, dtype=RESCUE_RESULT_DTYPE)
+    rec[0] = tuple(int(r[f]) for f in RESCUE_RESULT_DTYPE.names)
+    return rec
+
+
+def mate_rescue_window(record, ref_len, glen):
+    """drm_mate_rescue_window: the window id under which the aligners find a rescued hit (a status-0 record)."""
+    w = C.c_uint64(0)
+    check(lib().drm_mate_rescue_window(ptr(_rescue_record(record)), int(ref_len), int(glen), C.byref(w)))
+    return int(w.value)
+
+
+def pair_rescue_choose(pair, s1, s2, anchor1, anchor2, rA, rB, ref_len, glen, unpaired_penalty=17, min_score=0):
+    """drm_pair_rescue_choose: `pair` is one record of pair_hits, s1 / s2 and anchor1 / anchor2 the scores and window
+    ids of its chosen rows (0 where j = -1), rA / rB the rescue records anchored on mate 1's / mate 2's hit (None = no
+    task). Returns (record, rescued_id): the pair's record, with status 5 or 6 and the rescued mate's window id when a
+    rescue replaces the choice, unchanged (and 0) otherwise."""
+    p = np.zeros(1, dtype=PAIR_RESULT_DTYPE)
+    p[0] = tuple(int(pair[f]) for f in PAIR_RESULT_DTYPE.names)
+    a = None if rA is None else _rescue_record(rA)
+    b = None if rB is None else _rescue_record(rB)
+    out = np.zeros(1, dtype=PAIR_RESULT_DTYPE)
+    w = C.c_uint64(0)
+    check(lib().drm_pair_rescue_choose(ptr(p), int(s1), int(s2), int(anchor1), int(anchor2), ptr(a), ptr(b),
+                                       int(ref_len), int(glen), int(unpaired_penalty), int(min_score), ptr(out),
+                                       C.byref(w)))
+    return out[0], int(w.value)

@@ -449,6 +449,80 @@ typedef struct {
 } drm_sam_mate_fields;
 int drm_sam_pair_fields(const drm_sam_mate in[2], int proper, drm_sam_mate_fields out[2]);
 
+/* ---------------------------------------------------------------- Mate rescue (paired-end reads)
+ * A pair is proper only when both mates' true windows come through the embedding search and the rerank. Where one
+ * did not (a repeat, a long indel, a burst of errors, a hit outside the top k), the mate that did map is taken as an
+ * anchor and the other read is aligned, score only, against the stretch of genome in which the template length says
+ * it must lie. The reference has no paired mode, so this text is the definition.
+ * Region of a task with anchor id w, a = w >> 1, all arithmetic in 64 bits, dlo = max(0, min_tlen - ref_len) and
+ * dhi = max_tlen - ref_len (drm_pair_hits' range of pos(r) - pos(f)), glen the genome length:
+ *   a + ref_len > glen, or dhi < dlo: empty.
+ *   w even (the anchor is the forward hit; the mate is a reverse hit at a position in [a + dlo, a + dhi]):
+ *     genome[s, e) with s = min(glen, a + dlo), e = min(glen, a + dhi + ref_len), reverse-complemented as a whole with
+ *     the reference's comp_table; reverse = 1.
+ *   w odd (the anchor is the reverse hit; the mate is a forward hit at a position in [a - dhi, a - dlo]):
+ *     genome[s, e) with s = max(0, a - dhi), e = min(glen, a - dlo + ref_len), as it stands; reverse = 0.
+ *   e <= s: empty. An empty region is reported as region_start = 0, region_len = 0, reverse as above.
+ * dhi - dlo + ref_len > 2048 is DRM_ERR_UNSUPPORTED, decided from the parameters alone (the default 0,1000 template
+ * length gives 1,000 rows): with scores below 2^13, 11 bits of row and 8 of column the kernel's best-cell key fits
+ * 32 bits.
+ * Recurrence and end cell are drm_sw_align_affine's, word for word: Gotoh's H / E / F with the caller's scoring (the
+ * same accepted ranges), rows i = 1..n over the region as oriented, columns j = 1..m over the query bytes as passed
+ * (tags included, up to 256 bytes, DRM_ERR_UNSUPPORTED beyond), raw byte equality; score = max H, the end cell is,
+ * among the cells with H == score, the one of smallest i, then smallest j. There is no traceback.
+ * Record: region_start / region_len / reverse as above; score; ref_end / q_end = the end cell's i / j (exclusive
+ * ends, ref_end relative to the oriented region); status 0 = found, 1 = nothing (an empty region, score 0, or
+ * task_query outside [0, nq) on the device entry point): every field but the region's three is 0.
+ * Arguments: a genome handle (a window table: DRM_ERR_ARG); the pair parameters' ranges are drm_pair_hits', and
+ * ref_len must equal the handle's (DRM_ERR_ARG); unpaired_penalty is not used. The host form checks task_query and
+ * q_len as drm_sw_align does.
+ * Scores are comparable with the rerank's only under the rerank's scoring {1, 1, 0, 1}: a caller that weighs a rescued
+ * mate against reranked hits (drm_pair_rescue_choose) rescues with it. The scan visits every offset of the region, not
+ * only the stride grid of the window ids the search returns, so a rescued score can exceed the score of the best grid
+ * window over the same bases by the few columns the grid cuts off: this favours the rescued mate slightly. */
+typedef struct {
+    int64_t region_start;
+    int32_t region_len, reverse, score, ref_end, q_end, status;
+} drm_rescue_result;
+/* Task t aligns query task_query[t] (queries [nq x q_stride] bytes, q_len[nq]) against the region of anchor_ids[t];
+ * out[ntasks]. Host pointers. */
+int drm_mate_rescue(drm_refs *refs, const drm_sw_scoring *scoring, const drm_pair_params *p,
+                    const uint64_t *anchor_ids, const int64_t *task_query, int64_t ntasks, const uint8_t *queries,
+                    const int32_t *q_len, int32_t q_stride, int64_t nq, drm_rescue_result *out);
+/* Device-buffer form, enqueued on `stream`; query lengths are bounded by q_stride (<= 256). */
+int drm_mate_rescue_device(drm_refs *refs, const drm_sw_scoring *scoring, const drm_pair_params *p,
+                           const uint64_t *d_anchor_ids, const int64_t *d_task_query, int64_t ntasks,
+                           const uint8_t *d_queries, const int32_t *d_q_len, int32_t q_stride, int64_t nq,
+                           drm_rescue_result *d_out, void *stream);
+/* Host only, no device: the region of one anchor on a genome of glen bases (glen >= 0; the parameter errors are
+ * drm_mate_rescue's, the 2,048-row cap included). */
+int drm_mate_rescue_region(const drm_pair_params *p, int64_t glen, uint64_t anchor_id, int64_t *start, int32_t *len,
+                           int32_t *reverse);
+/* Host only: the window id under which drm_sw_align / drm_sw_align_affine find a rescued hit (status 0, DRM_ERR_ARG
+ * otherwise, also for glen < ref_len, ref_len < 1, a region outside [0, glen) or ref_end outside [1, region_len]):
+ * p =region_start + ref_end - ref_len for a forward region,
+ * p = region_start + region_len - ref_end for a reversed one, clamped to [0, glen - ref_len]; *window_id =
+ * 2 * p + reverse. In both orientations the alignment's last row is the window's last row, or lies inside the window
+ * after clamping, so drm_sw_align_affine(*window_id, flank F) contains the whole alignment whenever it deletes at
+ * most F genome bases. */
+int drm_mate_rescue_window(const drm_rescue_result *r, int32_t ref_len, int64_t glen, uint64_t *window_id);
+/* Host only: whether a rescued mate replaces what drm_pair_hits chose for a pair. s1 / s2 are the scores of the
+ * pair's chosen rows (0 for j = -1), anchor1 / anchor2 their window ids. rA is the rescue of mate 2 anchored on mate
+ * 1's chosen hit, rB the rescue of mate 1 anchored on mate 2's; NULL = no task. A record is valid when its status is
+ * 0 and its score >= min_score; sumA = s1 + rA->score, sumB = rB->score + s2.
+ *   pair status 0 or 4: unchanged.
+ *   pair status 1: a valid candidate qualifies when its sum >= s1 + s2 - unpaired_penalty, drm_pair_hits' test for a
+ *                  proper combination; the larger sum wins, rA on a tie.
+ *   pair status 2: rA qualifies when valid.     pair status 3: rB qualifies when valid.
+ * A winner: *out = the pair with status 5 (mate 2 rescued; j2 = -1) or 6 (mate 1 rescued; j1 = -1), score = the sum,
+ * tlen = pos(r) + ref_len - pos(f) from the anchor and the rescued window id w_r (drm_mate_rescue_window), which is
+ * returned in *rescued_id; j of the other mate and n_proper are kept. Otherwise *out = *pair and *rescued_id = 0.
+ * DRM_ERR_ARG: a null pair / out / rescued_id, a pair status outside [0, 4], or a winner that
+ * drm_mate_rescue_window rejects. */
+int drm_pair_rescue_choose(const drm_pair_result *pair, int32_t s1, int32_t s2, uint64_t anchor1, uint64_t anchor2,
+                           const drm_rescue_result *rA, const drm_rescue_result *rB, int32_t ref_len, int64_t glen,
+                           int32_t unpaired_penalty, int32_t min_score, drm_pair_result *out, uint64_t *rescued_id);
+
 /* ---------------------------------------------------------------- L2 rerank (the reference's live path)
  * post_process_l2_static (src/utils/post_processor.cpp:1023-1162, called at src/main.cpp:330) ->
  * find_sequences (static) -> Vectorizer::vectorize of the candidate windows -> batch_reranker(k = k_clusters)

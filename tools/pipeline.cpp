@@ -18,7 +18,9 @@
 // DRM_MATES=<fastq of second mates> (with use_dynamic=1 use_streaming=1 DRM_SAM_CIGAR=1) maps read pairs: the two files
 // are interleaved, searched and reranked as one batch, drm_pair_hits chooses one hit per mate (DRM_PAIR_TLEN=min,max,
 // DRM_PAIR_PENALTY=n), only those are aligned, and the SAM carries two lines per pair with the pair flags, RNEXT,
-// PNEXT and TLEN (drm_sam_pair_fields).
+// PNEXT and TLEN (drm_sam_pair_fields). DRM_PAIR_RESCUE=1 beside it rescues the mates the search lost: a pair without a
+// proper combination has each read aligned against the insert window of its mate's hit (drm_mate_rescue), and a
+// rescued mate that scores at least DRM_PAIR_RESCUE_MIN=n replaces the unpaired choice (drm_pair_rescue_choose).
 // Sequence inputs are embedded by the reference's GRU model on the GPU (drm_vectorize) when
 // DRM_ENCODER names it (.xml IR or .drmenc) or when the reference's models/ path exists in the working
 // directory (Config::Inference::MODEL_PATH); otherwise by the deterministic 3-mer stand-in. The rerank is
@@ -200,10 +202,15 @@ static bool affine_mode_from_env(size_t ref_len, AffineMode &mode)
 
 // DRM_MATES=<second mates> turns the paired mode on; DRM_PAIR_TLEN=min,max (default 0,1000) and DRM_PAIR_PENALTY=n
 // (default 17, bwa-mem's unpaired penalty) are read only then, as strictly as DRM_SAM_SCORING, and checked against
-// drm_pair_hits' ranges before any work.
+// drm_pair_hits' ranges before any work. DRM_PAIR_RESCUE=1 turns the mate rescue on; only then is DRM_PAIR_RESCUE_MIN=n
+// (0 to 2^20, the score a rescued mate needs) read, as strictly, and the template-length window checked against
+// drm_mate_rescue's 2,048-row cap.
+constexpr int32_t kRescueMinDefault = 49; // the largest chance score measured, 39, plus 10
 struct PairMode {
     std::string mates;
     drm_pair_params prm;
+    bool rescue = false;
+    int32_t rescue_min = kRescueMinDefault;
 };
 
 static bool pair_mode_from_env(size_t ref_len, PairMode &mode)
@@ -234,7 +241,72 @@ static bool pair_mode_from_env(size_t ref_len, PairMode &mode)
             throw drm::Error(DRM_ERR_ARG, std::string("DRM_PAIR_PENALTY must be an integer in [0, 2^20]: \"") + pe + "\"");
         mode.prm.unpaired_penalty = (int32_t)x;
     }
+    mode.rescue = std::getenv("DRM_PAIR_RESCUE") && std::atoi(std::getenv("DRM_PAIR_RESCUE")) != 0;
+    if (mode.rescue) {
+        if (const char *mi = std::getenv("DRM_PAIR_RESCUE_MIN")) {
+            long x = 0;
+            if (!parse_int(mi, x) || x > (1L << 20))
+                throw drm::Error(DRM_ERR_ARG,
+                                 std::string("DRM_PAIR_RESCUE_MIN must be an integer in [0, 2^20]: \"") + mi + "\"");
+            mode.rescue_min = (int32_t)x;
+        }
+        int64_t dlo = 0, dhi = 0;
+        drm::check_rescue_params(&mode.prm, dlo, dhi); // DRM_PAIR_TLEN wider than the rescue's 2,048 rows
+    }
     return true;
+}
+
+// DRM_PAIR_RESCUE=1, one block of pairs after drm_pair_hits: pair p's reads are the block's queries 2p and 2p + 1, their
+// rerank lists ids / scores [2 * npairs][k]. A pair of status 1 gives two tasks (mate 2 against the insert window of
+// mate 1's chosen hit, then mate 1 against that of mate 2's), status 2 / 3 one; drm_mate_rescue scores them with the
+// rerank's scoring and drm_pair_rescue_choose decides. A rescued mate's window id goes where its chosen row's id
+// would be in the list handed to the aligner, and its pair counts as proper.
+static void rescue_block(drm_refs *rt, const PairMode &mode, int64_t glen, const std::vector<drm_pair_result> &res,
+                         const uint64_t *ids, const int32_t *scores, size_t k, const uint8_t *queries,
+                         const int32_t *q_len, int32_t q_stride, std::vector<uint64_t> &chosen,
+                         std::vector<int32_t> &cnt, std::vector<int32_t> &proper)
+{
+    const size_t np = res.size();
+    auto row_id = [&](size_t read, int32_t j) { return j >= 0 ? ids[read * k + (size_t)j] : (uint64_t)0; };
+    auto row_score = [&](size_t read, int32_t j) { return j >= 0 ? scores[read * k + (size_t)j] : 0; };
+    std::vector<uint64_t> anchors;
+    std::vector<int64_t> tq, slot(2 * np, -1); // slot[2p] = the task anchored on mate 1 (rA), slot[2p + 1] on mate 2
+    for (size_t p = 0; p < np; ++p) {
+        const int32_t st = res[p].status;
+        if (st == 1 || st == 2) {
+            slot[2 * p] = (int64_t)anchors.size();
+            anchors.push_back(row_id(2 * p, res[p].j1));
+            tq.push_back((int64_t)(2 * p + 1));
+        }
+        if (st == 1 || st == 3) {
+            slot[2 * p + 1] = (int64_t)anchors.size();
+            anchors.push_back(row_id(2 * p + 1, res[p].j2));
+            tq.push_back((int64_t)(2 * p));
+        }
+    }
+    if (anchors.empty())
+        return;
+    const drm_sw_scoring rerank_scoring{1, 1, 0, 1};
+    std::vector<drm_rescue_result> out(anchors.size());
+    check(drm_mate_rescue(rt, &rerank_scoring, &mode.prm, anchors.data(), tq.data(), (int64_t)anchors.size(), queries,
+                          q_len, q_stride, (int64_t)(2 * np), out.data()));
+    for (size_t p = 0; p < np; ++p) {
+        if (slot[2 * p] < 0 && slot[2 * p + 1] < 0)
+            continue;
+        const drm_rescue_result *rA = slot[2 * p] >= 0 ? &out[(size_t)slot[2 * p]] : nullptr;
+        const drm_rescue_result *rB = slot[2 * p + 1] >= 0 ? &out[(size_t)slot[2 * p + 1]] : nullptr;
+        drm_pair_result r{};
+        uint64_t wr = 0;
+        check(drm_pair_rescue_choose(&res[p], row_score(2 * p, res[p].j1), row_score(2 * p + 1, res[p].j2),
+                                     row_id(2 * p, res[p].j1), row_id(2 * p + 1, res[p].j2), rA, rB, mode.prm.ref_len,
+                                     glen, mode.prm.unpaired_penalty, mode.rescue_min, &r, &wr));
+        if (r.status != 5 && r.status != 6)
+            continue;
+        const size_t read = 2 * p + (r.status == 5 ? 1 : 0);
+        chosen[read] = wr;
+        cnt[read] = 1;
+        proper[p] = 1;
+    }
 }
 
 int main(int argc, char *argv[])
@@ -635,6 +707,9 @@ int main(int argc, char *argv[])
                                 }
                             (*proper)[p] = res[p].status == 0;
                         }
+                        if (pair_mode.rescue)
+                            rescue_block(art, pair_mode, (int64_t)genome.size(), res, sw_ids.p + at, sw_scores.p + at,
+                                         (size_t)k, qbuf.p + lo * qs, ql.p + lo, (int32_t)qs, *ids, *cnt, *proper);
                         ba->align(art, ids->data(), cnt->data(), m, 1, qbuf.p + lo * qs, ql.p + lo, (int32_t)qs,
                                   (int32_t)ref_len, affine);
                     } catch (...) {
