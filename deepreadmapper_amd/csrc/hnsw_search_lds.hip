@@ -471,10 +471,14 @@ void launch_hnsw_search_lds(DeviceIndex &ix, const float *d_x, int64_t n, int k,
     // (re)allocate per-slot workspace
     const int64_t words = (ix.ntotal + 31) / 32;
     if (slots > ix.n_slots || words != ix.vis_words) {
-        if (ix.visited)
+        if (ix.visited) {
             DRM_HIP_CHECK(hipFree(ix.visited));
-        if (ix.clear_list)
+            ix.device_bytes -= (int64_t)sizeof(uint32_t) * ix.n_slots * ix.vis_words;
+        }
+        if (ix.clear_list) {
             DRM_HIP_CHECK(hipFree(ix.clear_list));
+            ix.device_bytes -= (int64_t)sizeof(int32_t) * ix.n_slots * ix.clear_cap;
+        }
         ix.visited = nullptr;
         ix.clear_list = nullptr;
         const int alloc_slots = std::max(slots, (int)std::min<int64_t>((int64_t)cus * per_cu, 1 << 20));
@@ -484,6 +488,8 @@ void launch_hnsw_search_lds(DeviceIndex &ix, const float *d_x, int64_t n, int k,
         DRM_HIP_CHECK(hipMemset(ix.visited, 0, sizeof(uint32_t) * (size_t)alloc_slots * (size_t)ix.vis_words));
         DRM_HIP_CHECK(hipMalloc(&ix.clear_list, sizeof(int32_t) * (size_t)alloc_slots * (size_t)ix.clear_cap));
         ix.n_slots = alloc_slots;
+        ix.device_bytes += (int64_t)sizeof(uint32_t) * alloc_slots * ix.vis_words +
+                           (int64_t)sizeof(int32_t) * alloc_slots * ix.clear_cap; // as launch_hnsw_search accounts for it
     }
     if (!ix.counter)
         DRM_HIP_CHECK(hipMalloc(&ix.counter, 4 * sizeof(uint32_t)));

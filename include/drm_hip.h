@@ -122,7 +122,13 @@ int drm_index_get_info(const drm_index *index, drm_index_info *info);
  * Host pointers: x [n x d] f32 row-major; D [n x k] f32 and I [n x k] int64 are caller-owned and
  * filled like faiss (ascending distance, ties by id, missing slots (+inf, -1)).
  * Throws-equivalent: n == 0 -> DRM_ERR_ARG "Query data is empty" (search.cpp:16-19).
- * stats may be NULL. */
+ * stats may be NULL.
+ * Limits (each DRM_ERR_UNSUPPORTED from the search, of drm_search_device[_ex] too; the handle stays usable):
+ * 1 <= k <= 1024; max(ef, k) <= 4096; level-0 degree 2 * M_hnsw <= 64 and every upper-level degree <= 64;
+ * a PQ distance table of M * 2^nbits <= 16384 entries (64 KB). Within them any PQ shape drm_index_load accepts
+ * is searched (nbits 1..16 in faiss's packed layout, any M dividing d). The table, and above max(ef, k) = 512
+ * the heaps beside it, live in one workgroup's dynamic LDS -- 105 KB at all three limits at once, which the
+ * gfx950 runtime grants without an opt-in (160 KB per workgroup); the queries need no alignment. */
 int drm_search(drm_index *index, const float *x, int64_t n, int32_t d, int32_t k, int32_t ef, float *D, int64_t *I,
                drm_search_stats *stats);
 

@@ -193,6 +193,32 @@ def test_device_entry_on_a_stream(c1, c1_ix, c1_adc):
             b.free()
 
 
+def test_device_entry_unaligned_queries(c1, c1_ix, c1_adc):
+    """d_x four bytes past a 16-byte boundary: the scan's fast8 switch needs aligned queries, so an 8 x 8 index then
+    takes the generic kernel (QT = 1, LUT in dynamic LDS) -- with the same rows."""
+    from deepreadmapper_amd.device import DeviceBuffer
+    q = c1["q"][:37]
+    n, d = q.shape
+    host = np.zeros(n * d + 4, dtype=np.float32)
+    host[1:1 + n * d] = q.ravel()
+    buf = DeviceBuffer.from_host(host)
+    assert buf.ptr % 16 == 0
+
+    class _At:
+        ptr = buf.ptr + 4
+
+    bufs = [buf]
+    try:
+        for k in (128, 1024):
+            d_D, d_I = DeviceBuffer((n, k), np.float32), DeviceBuffer((n, k), np.int64)
+            bufs += [d_D, d_I]
+            c1_ix.exact_search_device(_At, n, k, d_D, d_I)
+            same(d_D.download(), d_I.download(), c1_adc[0][:n, :k], c1_adc[1][:n, :k])
+    finally:
+        for b in bufs:
+            b.free()
+
+
 # ------------------------------------------------------------------ 6. generic PQ shape
 def test_generic_pq_shape(c1, tmp_path):
     from deepreadmapper_amd import read_index, synth
