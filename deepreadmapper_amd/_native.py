@@ -51,6 +51,8 @@ EXPORTS = [
     "drm_pair_hits", "drm_pair_hits_device", "drm_sam_pair_fields",
     "drm_mate_rescue", "drm_mate_rescue_device", "drm_mate_rescue_region", "drm_mate_rescue_window",
     "drm_pair_rescue_choose",
+    "drm_hit_mapq", "drm_hit_mapq_device", "drm_pair_mapq", "drm_pair_mapq_device", "drm_mapq_value",
+    "drm_pair_mapq_rescued",
 ]
 
 
@@ -214,6 +216,12 @@ def lib():
         "drm_mate_rescue_window": (C.c_int, [vp, i32, i64, C.POINTER(C.c_uint64)]),
         "drm_pair_rescue_choose": (C.c_int, [vp, i32, i32, C.c_uint64, C.c_uint64, vp, vp, i32, i64, i32, i32, vp,
                                               C.POINTER(C.c_uint64)]),
+        "drm_hit_mapq": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i32, vp]),
+        "drm_hit_mapq_device": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i32, vp, vp]),
+        "drm_pair_mapq": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i64, vp]),
+        "drm_pair_mapq_device": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i64, vp, vp]),
+        "drm_mapq_value": (C.c_int, [i64, i64, i64, i64, i64, C.POINTER(i32)]),
+        "drm_pair_mapq_rescued": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, vp]),
         "drm_exact_search": (C.c_int, [vp, vp, i64, i32, i32, vp, vp, C.POINTER(C.c_double)]),
         "drm_exact_search_device": (C.c_int, [vp, vp, i64, i32, vp, vp, vp]),
         "drm_exact_search_l2": (C.c_int, [vp, i64, i32, vp, i64, i32, vp, vp, C.POINTER(C.c_double)]),

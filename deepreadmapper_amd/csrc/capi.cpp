@@ -1943,6 +1943,154 @@ int drm_pair_hits(const drm_pair_params *p, const uint64_t *ids1, const int32_t 
     });
 }
 
+// ---------------------------------------------------------------------- mapping quality (mapq.hip)
+static drm::MapqArgs make_mapq_args(const drm_mapq_params *p, const uint64_t *ids, const int32_t *scores,
+                                    const int32_t *cnt, const int32_t *head, const int32_t *full, int64_t nreads,
+                                    int32_t k, drm_mapq_result *out)
+{
+    drm::check_mapq_params(p);
+    if (k < 0 || k > drm::kMaxCands)
+        throw Error(DRM_ERR_UNSUPPORTED, "k = " + std::to_string(k) + " outside [0, 1024], the rerank's candidate cap");
+    if (nreads < 0)
+        throw Error(DRM_ERR_ARG, "nreads must be >= 0");
+    if (nreads > 0 && (!cnt || !full || !out || (k > 0 && (!ids || !scores))))
+        throw Error(DRM_ERR_ARG, "null argument");
+    return drm::MapqArgs{*p, ids, scores, cnt, head, full, nreads, k, out};
+}
+
+// the counted rows' scores of `n` lists `step` rows apart, before anything reaches the device
+static void check_list_scores(const int32_t *cnt, const int32_t *sc, int64_t n, int64_t step, int32_t k, const char *what)
+{
+    for (int64_t q = 0; q < n; ++q) {
+        const int64_t row = q * step;
+        const int32_t c = std::min(std::max(cnt[row], 0), k);
+        for (int32_t j = 0; j < c; ++j)
+            if (sc[row * k + j] < 0 || sc[row * k + j] > (1 << 20))
+                throw Error(DRM_ERR_ARG, std::string(what) + " " + std::to_string(q) + ", row " + std::to_string(j) +
+                                             ": score " + std::to_string(sc[row * k + j]) + " outside [0, 2^20]");
+    }
+}
+
+int drm_hit_mapq_device(const drm_mapq_params *p, const uint64_t *d_ids, const int32_t *d_scores, const int32_t *d_cnt,
+                        const int32_t *d_head, const int32_t *d_full, int64_t nreads, int32_t k,
+                        drm_mapq_result *d_out, void *stream)
+{
+    return guarded([&] {
+        const drm::MapqArgs a = make_mapq_args(p, d_ids, d_scores, d_cnt, d_head, d_full, nreads, k, d_out);
+        drm::launch_hit_mapq(a, (hipStream_t)stream);
+    });
+}
+
+int drm_hit_mapq(const drm_mapq_params *p, const uint64_t *ids, const int32_t *scores, const int32_t *cnt,
+                 const int32_t *head, const int32_t *full, int64_t nreads, int32_t k, drm_mapq_result *out)
+{
+    return guarded([&] {
+        drm::MapqArgs a = make_mapq_args(p, ids, scores, cnt, head, full, nreads, k, out);
+        if (nreads == 0)
+            return;
+        check_list_scores(cnt, scores, nreads, 1, k, "read");
+        DevBuf<uint64_t> di((size_t)nreads * (size_t)k);
+        DevBuf<int32_t> ds((size_t)nreads * (size_t)k), dc((size_t)nreads), dh(head ? (size_t)nreads : 0),
+            df((size_t)nreads);
+        DevBuf<drm_mapq_result> dout((size_t)nreads);
+        if (k > 0) {
+            di.upload(ids);
+            ds.upload(scores);
+        }
+        dc.upload(cnt);
+        df.upload(full);
+        if (head)
+            dh.upload(head);
+        a.ids = di.p;
+        a.scores = ds.p;
+        a.cnt = dc.p;
+        a.head = head ? dh.p : nullptr;
+        a.full = df.p;
+        a.out = dout.p;
+        drm::launch_hit_mapq(a, nullptr);
+        DRM_HIP_CHECK(hipDeviceSynchronize());
+        dout.download(out);
+    });
+}
+
+int drm_pair_mapq_device(const drm_pair_params *pp, const drm_mapq_params *mp, const uint64_t *d_ids1,
+                         const int32_t *d_scores1, const int32_t *d_cnt1, const uint64_t *d_ids2,
+                         const int32_t *d_scores2, const int32_t *d_cnt2, const int32_t *d_full1,
+                         const int32_t *d_full2, const drm_pair_result *d_pairs, int64_t npairs, int32_t k,
+                         int64_t row_step, drm_pair_mapq_result *d_out, void *stream)
+{
+    return guarded([&] {
+        drm_pair_result unused{};
+        drm::PairMapqArgs a{};
+        a.pair = make_pair_args(pp, d_ids1, d_scores1, d_cnt1, d_ids2, d_scores2, d_cnt2, npairs, k, row_step, &unused);
+        a.pair.out = nullptr;
+        drm::check_mapq_params(mp);
+        if (npairs > 0 && (!d_full1 || !d_full2 || !d_pairs || !d_out))
+            throw Error(DRM_ERR_ARG, "null argument");
+        a.prm = *mp;
+        a.full1 = d_full1;
+        a.full2 = d_full2;
+        a.pairs = d_pairs;
+        a.out = d_out;
+        drm::launch_pair_mapq(a, (hipStream_t)stream);
+    });
+}
+
+int drm_pair_mapq(const drm_pair_params *pp, const drm_mapq_params *mp, const uint64_t *ids1, const int32_t *scores1,
+                  const int32_t *cnt1, const uint64_t *ids2, const int32_t *scores2, const int32_t *cnt2,
+                  const int32_t *full1, const int32_t *full2, const drm_pair_result *pairs, int64_t npairs, int32_t k,
+                  int64_t row_step, drm_pair_mapq_result *out)
+{
+    return guarded([&] {
+        drm_pair_result unused{};
+        drm::PairMapqArgs a{};
+        a.pair = make_pair_args(pp, ids1, scores1, cnt1, ids2, scores2, cnt2, npairs, k, row_step, &unused);
+        a.pair.out = nullptr;
+        drm::check_mapq_params(mp);
+        if (npairs > 0 && (!full1 || !full2 || !pairs || !out))
+            throw Error(DRM_ERR_ARG, "null argument");
+        if (npairs == 0)
+            return;
+        for (int64_t q = 0; q < npairs; ++q)
+            if (pairs[q].status < 0 || pairs[q].status > 4)
+                throw Error(DRM_ERR_ARG, "pair " + std::to_string(q) + ": status " + std::to_string(pairs[q].status) +
+                                             " outside [0, 4]");
+        check_list_scores(cnt1, scores1, npairs, row_step, k, "mate 1 of pair");
+        check_list_scores(cnt2, scores2, npairs, row_step, k, "mate 2 of pair");
+        // each mate's lists span ((npairs - 1) * row_step + 1) rows from its own base pointer (the two may overlap)
+        const size_t rows = (size_t)(npairs - 1) * (size_t)row_step + 1;
+        DevBuf<uint64_t> di1(rows * (size_t)k), di2(rows * (size_t)k);
+        DevBuf<int32_t> ds1(rows * (size_t)k), ds2(rows * (size_t)k), dc1(rows), dc2(rows), df1(rows), df2(rows);
+        DevBuf<drm_pair_result> dp((size_t)npairs);
+        DevBuf<drm_pair_mapq_result> dout((size_t)npairs);
+        if (k > 0) {
+            di1.upload(ids1);
+            di2.upload(ids2);
+            ds1.upload(scores1);
+            ds2.upload(scores2);
+        }
+        dc1.upload(cnt1);
+        dc2.upload(cnt2);
+        df1.upload(full1);
+        df2.upload(full2);
+        dp.upload(pairs);
+        a.pair.ids1 = di1.p;
+        a.pair.ids2 = di2.p;
+        a.pair.scores1 = ds1.p;
+        a.pair.scores2 = ds2.p;
+        a.pair.cnt1 = dc1.p;
+        a.pair.cnt2 = dc2.p;
+        a.prm = *mp;
+        a.full1 = df1.p;
+        a.full2 = df2.p;
+        a.pairs = dp.p;
+        a.out = dout.p;
+        drm::launch_pair_mapq(a, nullptr);
+        DRM_HIP_CHECK(hipDeviceSynchronize());
+        dout.download(out);
+    });
+}
+
 // ---------------------------------------------------------------------- mate rescue (mate_rescue.hip)
 static drm::RescueArgs make_rescue_args(const drm_refs *refs, const drm_sw_scoring *sc, const drm_pair_params *p,
                                         const uint64_t *anchors, const int64_t *tq, int64_t ntasks, const uint8_t *q,

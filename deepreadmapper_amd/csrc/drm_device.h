@@ -351,6 +351,30 @@ struct RescueArgs {
 };
 void launch_mate_rescue(int device, const RescueArgs &a, int max_qlen, hipStream_t stream);
 
+// Mapping quality (mapq.hip; drm_hit_mapq, drm_pair_mapq): one wave per read / per pair, the
+// locus scan of a hit list and, for pairs, the best proper combination outside the chosen loci. Both run on the current
+// device and throw Error(DRM_ERR_UNSUPPORTED) for k outside [0, kMaxCands].
+struct MapqArgs {
+    drm_mapq_params prm;
+    const uint64_t *ids;   // [nreads][k]
+    const int32_t *scores; // [nreads][k]
+    const int32_t *cnt;    // [nreads]
+    const int32_t *head;   // [nreads] or null (= -1, the top hit)
+    const int32_t *full;   // [nreads]
+    int64_t nreads;
+    int32_t k;
+    drm_mapq_result *out; // [nreads]
+};
+void launch_hit_mapq(const MapqArgs &a, hipStream_t stream);
+struct PairMapqArgs {
+    PairArgs pair; // the lists in drm_pair_hits' layout; `out` is not used
+    drm_mapq_params prm;
+    const int32_t *full1, *full2;  // indexed like cnt1 / cnt2
+    const drm_pair_result *pairs;  // [npairs] drm_pair_hits' records
+    drm_pair_mapq_result *out;     // [npairs]
+};
+void launch_pair_mapq(const PairMapqArgs &a, hipStream_t stream);
+
 // L2 rerank (post_process_l2_static -> batch_reranker, src/utils/post_processor.cpp:1023-1162,
 // src/utils/reranker.cpp:98-195): distances from the window embedding table, libstdc++ partial_sort
 struct L2Args {

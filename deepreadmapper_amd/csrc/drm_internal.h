@@ -155,10 +155,12 @@ struct SamAlignments {
     const int64_t *region_start = nullptr;
     const int32_t *region_len = nullptr;
 };
+// `mapq` (DRM_SAM_MAPQ, null = "60" on every line): the MAPQ column of the block's rows, mapq[i * k + j] for row j of
+// query i; a row written unmapped prints 0.
 void write_sam_block(const std::string &path, bool header, const std::string &ref_name, size_t ref_len,
                      const std::vector<std::string> &query_seqs, const std::vector<std::string> &query_ids,
                      size_t q0, size_t nq, const uint64_t *ids, const int32_t *counts, size_t k,
-                     const SamAlignments *aln = nullptr);
+                     const SamAlignments *aln = nullptr, const int32_t *mapq = nullptr);
 // The paired form (DRM_MATES, no reference counterpart): the two primary lines of pairs whose reads are queries
 // q0 + 2 * p (mate 1) and q0 + 2 * p + 1 (mate 2). Row r = 2 * p + m of the block carries the read's chosen window
 // ids[r] (counts[r] = 1, or 0 for a read without a hit) and its alignment aln.rec[r] as in the DRM_SAM_CIGAR mode
@@ -166,10 +168,11 @@ void write_sam_block(const std::string &path, bool header, const std::string &re
 // chose a proper combination. The fields that relate the two lines are drm_sam_pair_fields' (include/drm_hip.h):
 //   mapped:   QNAME FLAG ref POS 60 CIGAR = PNEXT TLEN SEQ * AS:i:<score> NM:i:<nm>
 //   unmapped: QNAME FLAG ref|* POS 60 * =|* PNEXT TLEN SEQ *        (SEQ as read; "*" when neither mate is mapped)
+// `mapq` (null = "60"): mapq[r] for the line of row r; an unmapped mate prints 0.
 void write_sam_pairs(const std::string &path, bool header, const std::string &ref_name, size_t ref_len,
                      const std::vector<std::string> &query_seqs, const std::vector<std::string> &query_ids,
                      size_t q0, size_t npairs, const uint64_t *ids, const int32_t *counts, const int32_t *proper,
-                     const SamAlignments &aln);
+                     const SamAlignments &aln, const int32_t *mapq = nullptr);
 
 // Mate rescue (include/drm_hip.h, drm_mate_rescue): the region of one anchor id, the one statement of the rule that
 // the host entry points (formats.cpp) and the kernel (mate_rescue.hip) both compile. dlo / dhi are
@@ -210,6 +213,23 @@ DRM_HOST_DEVICE inline RescueRegion rescue_region(uint64_t w, int64_t glen, int3
 }
 // drm_pair_hits' ranges of ref_len and the template lengths, and the rescue's row cap; returns dlo / dhi
 void check_rescue_params(const drm_pair_params *p, int64_t &dlo, int64_t &dhi);
+
+// Mapping quality (include/drm_hip.h, drm_mapq_value): the one statement of the formula that the host entry points
+// (formats.cpp) and the kernels (mapq.hip) both compile. Arguments within [-2^20, 2^20]: 60 * 2^20 * 2^20 < 2^63.
+DRM_HOST_DEVICE inline int32_t mapq_value(int64_t s1, int64_t sub, int64_t n_sub, int64_t full, int64_t min_score)
+{
+    if (s1 <= 0 || full <= 0)
+        return 0;
+    const int64_t c = s1 < full ? s1 : full, s2 = sub > min_score ? sub : min_score;
+    if (c <= s2)
+        return 0;
+    int64_t q = (60 * (c - s2) * c) / ((c - min_score) * full);
+    for (int64_t x = n_sub + 1; x > 1; x >>= 1) // 3 * floor(log2(n_sub + 1))
+        q -= 3;
+    return (int32_t)(q < 0 ? 0 : q > 60 ? 60 : q);
+}
+// drm_mapq_params' accepted ranges (DRM_ERR_ARG)
+void check_mapq_params(const drm_mapq_params *p);
 
 void build_hnswpq(const float *x, int64_t n, int d, int M_pq, int nbits, int M_hnsw, int efc, double sample_rate,
                   int nthreads, uint64_t seed, const std::string &path);

@@ -402,7 +402,7 @@ extern "C" int drm_sam_cigar(const drm_sw_alignment *a, const uint32_t *ops, int
 // alignment is written as unmapped
 static void append_aligned_row(std::string &buf, const std::string &qname, int flag, const std::string &ref_name,
                                size_t ref_len, const std::string &tagged, uint64_t sid,
-                               const drm::SamAlignments &aln, size_t row)
+                               const drm::SamAlignments &aln, size_t row, const int32_t *mapq)
 {
     const drm_sw_alignment &a = aln.rec[row];
     // the read is the query without format_fastq's tags (an untagged .txt query is the read itself)
@@ -425,7 +425,9 @@ static void append_aligned_row(std::string &buf, const std::string &qname, int f
     buf += ref_name;
     buf += '\t';
     buf += std::to_string(pos1);
-    buf += "\t60\t";
+    buf += '\t';
+    buf += mapq ? std::to_string(a.status == 1 ? 0 : mapq[row]) : std::string("60");
+    buf += '\t';
     buf += cigar;
     buf += "\t*\t0\t0\t";
     buf += clean.empty() ? std::string("*") : (flag & 16) ? drm::reverse_complement(clean) : clean;
@@ -441,7 +443,7 @@ static void append_aligned_row(std::string &buf, const std::string &qname, int f
 void drm::write_sam_block(const std::string &path, bool header, const std::string &ref_name, size_t ref_len,
                           const std::vector<std::string> &query_seqs, const std::vector<std::string> &query_ids,
                           size_t q0, size_t nq, const uint64_t *ids, const int32_t *counts, size_t k,
-                          const SamAlignments *aln)
+                          const SamAlignments *aln, const int32_t *mapq)
 {
     std::ofstream out(path, header ? std::ios::out : std::ios::app);
     if (!out.is_open())
@@ -465,7 +467,8 @@ void drm::write_sam_block(const std::string &path, bool header, const std::strin
             if (sid % 2 == 1)
                 flag |= 16; // reverse complement
             if (aln) {
-                append_aligned_row(buf, qname, flag, ref_name, ref_len, query_seqs[g], sid, *aln, i * k + (size_t)j);
+                append_aligned_row(buf, qname, flag, ref_name, ref_len, query_seqs[g], sid, *aln, i * k + (size_t)j,
+                                   mapq);
                 continue;
             }
             buf += qname;
@@ -475,7 +478,9 @@ void drm::write_sam_block(const std::string &path, bool header, const std::strin
             buf += ref_name;
             buf += '\t';
             buf += std::to_string(sid / 2 + 1); // 1-based position
-            buf += "\t60\t";
+            buf += '\t';
+            buf += mapq ? std::to_string(mapq[i * k + (size_t)j]) : std::string("60");
+            buf += '\t';
             buf += cigar;
             buf += "\t*\t0\t0\t";
             buf += clean;
@@ -670,10 +675,92 @@ extern "C" int drm_pair_rescue_choose(const drm_pair_result *pair, int32_t s1, i
     }
 }
 
+// ----------------------------------------------------------------------- mapping quality: the host-only parts
+void drm::check_mapq_params(const drm_mapq_params *p)
+{
+    if (!p)
+        throw Error(DRM_ERR_ARG, "null MAPQ parameters");
+    if (p->ref_len < 1 || p->ref_len > (1 << 20))
+        throw Error(DRM_ERR_ARG, "ref_len " + std::to_string(p->ref_len) + " outside [1, 2^20]");
+    if (p->locus_span < 1 || p->locus_span > (1 << 20))
+        throw Error(DRM_ERR_ARG, "locus_span " + std::to_string(p->locus_span) + " outside [1, 2^20]");
+    if (p->min_score < 0 || p->min_score > (1 << 20))
+        throw Error(DRM_ERR_ARG, "min_score " + std::to_string(p->min_score) + " outside [0, 2^20]");
+    if (p->sub_band < 0 || p->sub_band > (1 << 20))
+        throw Error(DRM_ERR_ARG, "sub_band " + std::to_string(p->sub_band) + " outside [0, 2^20]");
+}
+
+static int32_t mapq_value_checked(int64_t s1, int64_t sub, int64_t n_sub, int64_t full, int64_t min_score)
+{
+    using drm::Error;
+    constexpr int64_t lim = (int64_t)1 << 20;
+    if (n_sub < 0 || n_sub > lim)
+        throw Error(DRM_ERR_ARG, "n_sub " + std::to_string(n_sub) + " outside [0, 2^20]");
+    if (min_score < 0 || min_score > lim)
+        throw Error(DRM_ERR_ARG, "min_score " + std::to_string(min_score) + " outside [0, 2^20]");
+    if (s1 < -lim || s1 > lim || sub < -lim || sub > lim || full < -lim || full > lim)
+        throw Error(DRM_ERR_ARG, "s1, sub and full must lie in [-2^20, 2^20]");
+    return drm::mapq_value(s1, sub, n_sub, full, min_score);
+}
+
+extern "C" int drm_mapq_value(int64_t s1, int64_t sub, int64_t n_sub, int64_t full, int64_t min_score, int32_t *mapq)
+{
+    try {
+        if (!mapq)
+            throw drm::Error(DRM_ERR_ARG, "null argument");
+        *mapq = mapq_value_checked(s1, sub, n_sub, full, min_score);
+        return DRM_OK;
+    } catch (const drm::Error &e) {
+        drm::set_last_error(e.what());
+        return e.code;
+    } catch (const std::exception &e) {
+        drm::set_last_error(e.what());
+        return DRM_ERR_ARG;
+    }
+}
+
+extern "C" int drm_pair_mapq_rescued(const drm_mapq_params *mp, const drm_pair_result *pairs,
+                                     const int32_t *rescue_score, const int32_t *full1, const int32_t *full2,
+                                     int64_t npairs, int64_t row_step, drm_pair_mapq_result *inout)
+{
+    try {
+        using drm::Error;
+        drm::check_mapq_params(mp);
+        if (npairs < 0 || row_step < 1)
+            throw Error(DRM_ERR_ARG, "npairs must be >= 0 and row_step >= 1");
+        if (npairs > 0 && (!pairs || !rescue_score || !full1 || !full2 || !inout))
+            throw Error(DRM_ERR_ARG, "null argument");
+        // everything is checked before anything is written
+        std::vector<int32_t> q((size_t)npairs, 0);
+        for (int64_t p = 0; p < npairs; ++p) {
+            const int32_t st = pairs[p].status;
+            if (st < 0 || st > 6)
+                throw Error(DRM_ERR_ARG, "pair " + std::to_string(p) + ": status " + std::to_string(st) +
+                                             " outside [0, 6]");
+            if (st == 5 || st == 6)
+                q[(size_t)p] = mapq_value_checked(rescue_score[p], 0, 0, (st == 5 ? full2 : full1)[p * row_step],
+                                                  mp->min_score);
+        }
+        for (int64_t p = 0; p < npairs; ++p) {
+            if (pairs[p].status == 5)
+                inout[p].mapq2 = std::min(inout[p].mapq1, q[(size_t)p]);
+            else if (pairs[p].status == 6)
+                inout[p].mapq1 = std::min(inout[p].mapq2, q[(size_t)p]);
+        }
+        return DRM_OK;
+    } catch (const drm::Error &e) {
+        drm::set_last_error(e.what());
+        return e.code;
+    } catch (const std::exception &e) {
+        drm::set_last_error(e.what());
+        return DRM_ERR_ARG;
+    }
+}
+
 void drm::write_sam_pairs(const std::string &path, bool header, const std::string &ref_name, size_t ref_len,
                           const std::vector<std::string> &query_seqs, const std::vector<std::string> &query_ids,
                           size_t q0, size_t npairs, const uint64_t *ids, const int32_t *counts, const int32_t *proper,
-                          const SamAlignments &aln)
+                          const SamAlignments &aln, const int32_t *mapq)
 {
     std::ofstream out(path, header ? std::ios::out : std::ios::app);
     if (!out.is_open())
@@ -719,7 +806,9 @@ void drm::write_sam_pairs(const std::string &path, bool header, const std::strin
             buf += f[m].has_rname ? ref_name : std::string("*");
             buf += '\t';
             buf += std::to_string(f[m].pos);
-            buf += "\t60\t";
+            buf += '\t';
+            buf += mapq ? std::to_string(in[m].mapped ? mapq[2 * p + (size_t)m] : 0) : std::string("60");
+            buf += '\t';
             buf += in[m].mapped ? cigar[m] : std::string("*");
             buf += f[m].has_rname ? "\t=\t" : "\t*\t";
             buf += std::to_string(f[m].pnext);

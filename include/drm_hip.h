@@ -529,6 +529,95 @@ int drm_pair_rescue_choose(const drm_pair_result *pair, int32_t s1, int32_t s2, 
                            const drm_rescue_result *rA, const drm_rescue_result *rB, int32_t ref_len, int64_t glen,
                            int32_t unpaired_penalty, int32_t min_score, drm_pair_result *out, uint64_t *rescued_id);
 
+/* ---------------------------------------------------------------- Mapping quality (MAPQ)
+ * How certain a read's chosen hit is, from the hits that compete with it. The reference prints MAPQ 60 on every line
+ * and has no such step, so this text is the definition.
+ * Hit model (drm_pair_hits', word for word): a hit is a row (w, s) of a read's rerank output, pos(w) = w >> 1 (int64),
+ * rev(w) = w & 1. Only the first `count` rows of a list take part, a count outside [0, k] being clamped, and of those
+ * only the live ones, s > 0. Row indices always refer to the original list. The top of a set of rows is the row of
+ * largest s, the smallest row among equals. 0 <= k <= 1024 (beyond: DRM_ERR_UNSUPPORTED). Scores of the counted rows
+ * must lie in [0, 2^20]: the host forms check it (DRM_ERR_ARG), for the device forms it is the caller's contract.
+ * Parameters (DRM_ERR_ARG outside): 1 <= ref_len <= 2^20, 1 <= locus_span <= 2^20, 0 <= min_score <= 2^20,
+ * 0 <= sub_band <= 2^20.
+ * Same locus: rows a and b are in the same locus iff rev(a) == rev(b) and |pos(a) - pos(b)| < locus_span, in 64-bit
+ * arithmetic (positions are below 2^63: any u64 id is safe). At stride 1 the windows beside the true one overlap it
+ * and score almost as high; they are one locus, not competitors.
+ * The locus scan of one list with head row h (h = -1: the list's top hit; a given h must be a live counted row,
+ * otherwise the record is the "nothing" record):
+ *   1. locus 0 = every live row in the same locus as h, h included; locus_rows = their number, best = h,
+ *      best_score = s(h);
+ *   2. locus 0 is removed. sub_row = the top of what remains, or -1; sub_score = s(sub_row), or 0;
+ *   3. n_sub counts greedily: take the top t of what remains; stop when nothing remains or
+ *      s(t) < sub_score - sub_band; otherwise count one, remove every remaining row in the same locus as t, repeat.
+ *      So n_sub >= 1 exactly when sub_score > 0.
+ * The suppression is greedy, not transitive: rows at positions 0, 100, 200 of one strand with scores 100, 90, 80 and a
+ * span of 150 give locus 0 = {0, 100} and the row at 200 as the competitor.
+ * Record: status 0 = a head exists; status 1 = nothing: best = sub_row = -1, every other field 0.
+ * mapq = drm_mapq_value(best_score, sub_score, n_sub, full, min_score), a pure function in int64:
+ *   1. 0 if s1 <= 0 or full <= 0;
+ *   2. c = min(s1, full), s2 = max(sub, min_score);
+ *   3. 0 if c <= s2;
+ *   4. q = floor(60 * (c - s2) * c / ((c - min_score) * full)): the divisor is positive because c > s2 >= min_score,
+ *      and q <= 60 because c - s2 <= c - min_score and c <= full;
+ *   5. q -= 3 * floor(log2(n_sub + 1));
+ *   6. clamped to [0, 60].
+ * `full` is the score of the read against itself under the rerank's scoring {1, 1, 0, 1}: its length without tags.
+ * A perfect unique read gets 60, a unique read at 130 of 150 gets 52, a read whose competitor scores the
+ * same gets 0. */
+typedef struct {
+    int32_t ref_len, locus_span, min_score, sub_band;
+} drm_mapq_params;
+typedef struct {
+    int32_t best, best_score, locus_rows, sub_row, sub_score, n_sub, mapq, status;
+} drm_mapq_result;
+/* Read r's list is ids / scores + r * k with the count cnt[r]; head[r] its head row (head == NULL: -1 for every
+ * read), full[r] its self score. out[nreads]. Host pointers; runs on the current device. */
+int drm_hit_mapq(const drm_mapq_params *p, const uint64_t *ids, const int32_t *scores, const int32_t *cnt,
+                 const int32_t *head, const int32_t *full, int64_t nreads, int32_t k, drm_mapq_result *out);
+/* Device-buffer form, enqueued on `stream`. Stateless: no handle, the current device. It consumes
+ * drm_post_process_sw_{static,dynamic}_device's d_top_ids, d_top_scores and d_status unchanged. */
+int drm_hit_mapq_device(const drm_mapq_params *p, const uint64_t *d_ids, const int32_t *d_scores, const int32_t *d_cnt,
+                        const int32_t *d_head, const int32_t *d_full, int64_t nreads, int32_t k,
+                        drm_mapq_result *d_out, void *stream);
+/* Host only, no device: drm_mapq_value as defined above. DRM_ERR_ARG: a null mapq, n_sub < 0, min_score outside
+ * [0, 2^20], or |s1|, |sub|, n_sub or |full| beyond 2^20 (the products stay far inside int64). */
+int drm_mapq_value(int64_t s1, int64_t sub, int64_t n_sub, int64_t full, int64_t min_score, int32_t *mapq);
+/* Pair MAPQ. The two lists in drm_pair_hits' layout (row_step included), full_m indexed like cnt_m
+ * (full_m[p * row_step]), pairs[npairs] the records of drm_pair_hits on the same lists and pair parameters, whose
+ * statuses must be 0 to 4 (the host form: DRM_ERR_ARG; a device record outside gives the all-zero record). For pair p:
+ *   1. q_se_m = the locus scan's mapq of mate m's list with head = the pair's chosen row j_m; 0 for j_m = -1;
+ *   2. status 0 only: sub_pair = the largest s1 + s2 over the proper combinations (j1', j2') (drm_pair_hits'
+ *      definition of proper), except those where j1' is in the chosen j1's locus AND j2' is in the chosen j2's locus
+ *      (locus 0 of the two scans); 0 if none remain;
+ *   3. with t1, t2 the mates' top hits, subo = max(sub_pair, s(t1) + s(t2) - unpaired_penalty);
+ *   4. q_pe = clamp(6 * (score - subo), 0, 60), score the record's;
+ *   5. mapq_m = q_se_m if q_se_m > q_pe, otherwise min(q_pe, q_se_m + 40): bwa-mem's rule for letting a confident pair
+ *      lift an ambiguous mate;
+ *   6. statuses 1 to 3: mapq_m = q_se_m, q_pe = 0, sub_pair = 0;
+ *   7. status 4: every field 0. */
+typedef struct {
+    int32_t mapq1, mapq2, q_se1, q_se2, q_pe, sub_pair;
+} drm_pair_mapq_result;
+int drm_pair_mapq(const drm_pair_params *pp, const drm_mapq_params *mp, const uint64_t *ids1, const int32_t *scores1,
+                  const int32_t *cnt1, const uint64_t *ids2, const int32_t *scores2, const int32_t *cnt2,
+                  const int32_t *full1, const int32_t *full2, const drm_pair_result *pairs, int64_t npairs, int32_t k,
+                  int64_t row_step, drm_pair_mapq_result *out);
+int drm_pair_mapq_device(const drm_pair_params *pp, const drm_mapq_params *mp, const uint64_t *d_ids1,
+                         const int32_t *d_scores1, const int32_t *d_cnt1, const uint64_t *d_ids2,
+                         const int32_t *d_scores2, const int32_t *d_cnt2, const int32_t *d_full1,
+                         const int32_t *d_full2, const drm_pair_result *d_pairs, int64_t npairs, int32_t k,
+                         int64_t row_step, drm_pair_mapq_result *d_out, void *stream);
+/* Host only, plain loops: the MAPQ of rescued pairs. pairs[npairs] are the records after drm_pair_rescue_choose
+ * (statuses 0 to 6, DRM_ERR_ARG otherwise), inout[npairs] the drm_pair_mapq records of the pre-rescue pairs. A pair of
+ * status 5 (mate 2 rescued, mate 1 the anchor) keeps mapq1 and gets
+ * mapq2 = min(mapq1, drm_mapq_value(rescue_score[p], 0, 0, full2[p * row_step], min_score)); status 6 the mirror image
+ * with full1[p * row_step] (full_m indexed as in drm_pair_mapq): a rescued placement is never more certain than its
+ * anchor. rescue_score[p] is the rescued mate's own score (the record's sum minus the anchor's score). Every other
+ * field and every other pair is left as it is; rescue_score / full of an unrescued pair are not read. */
+int drm_pair_mapq_rescued(const drm_mapq_params *mp, const drm_pair_result *pairs, const int32_t *rescue_score,
+                          const int32_t *full1, const int32_t *full2, int64_t npairs, int64_t row_step,
+                          drm_pair_mapq_result *inout);
+
 /* ---------------------------------------------------------------- L2 rerank (the reference's live path)
  * post_process_l2_static (src/utils/post_processor.cpp:1023-1162, called at src/main.cpp:330) ->
  * find_sequences (static) -> Vectorizer::vectorize of the candidate windows -> batch_reranker(k = k_clusters)

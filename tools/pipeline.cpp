@@ -21,6 +21,9 @@
 // PNEXT and TLEN (drm_sam_pair_fields). DRM_PAIR_RESCUE=1 beside it rescues the mates the search lost: a pair without a
 // proper combination has each read aligned against the insert window of its mate's hit (drm_mate_rescue), and a
 // rescued mate that scores at least DRM_PAIR_RESCUE_MIN=n replaces the unpaired choice (drm_pair_rescue_choose).
+// DRM_SAM_MAPQ=1 (with use_dynamic=1 use_streaming=1 DRM_SAM_CIGAR=1, one device) replaces the constant MAPQ 60 by the
+// locus scan of each read's rerank rows (drm_hit_mapq; for pairs drm_pair_mapq and drm_pair_mapq_rescued), with
+// DRM_MAPQ_MIN=n and DRM_MAPQ_SPAN=n; the SW rerank then runs whatever the stride, as with DRM_MATES.
 // Sequence inputs are embedded by the reference's GRU model on the GPU (drm_vectorize) when
 // DRM_ENCODER names it (.xml IR or .drmenc) or when the reference's models/ path exists in the working
 // directory (Config::Inference::MODEL_PATH); otherwise by the deterministic 3-mer stand-in. The rerank is
@@ -256,15 +259,55 @@ static bool pair_mode_from_env(size_t ref_len, PairMode &mode)
     return true;
 }
 
+// DRM_SAM_MAPQ=1 (with use_dynamic=1 use_streaming=1 DRM_SAM_CIGAR=1 only): the MAPQ column comes from the locus scan of
+// each read's rerank rows (drm_hit_mapq, drm_pair_mapq) instead of the constant 60. DRM_MAPQ_MIN=n (default 39, the
+// largest chance score DESIGN.md sec. 4.11 recorded for 150-base reads) and DRM_MAPQ_SPAN=n (default ref_len) are read
+// only then, as strictly as DRM_SAM_SCORING; sub_band is 2, one substitution under the rerank's scoring {1, 1, 0, 1}.
+constexpr int32_t kMapqMinDefault = 39;
+static bool mapq_mode_from_env(size_t ref_len, drm_mapq_params &prm)
+{
+    const char *on = std::getenv("DRM_SAM_MAPQ");
+    if (!on || std::atoi(on) == 0)
+        return false;
+    if (ref_len < 1 || ref_len > ((size_t)1 << 20))
+        throw drm::Error(DRM_ERR_UNSUPPORTED, "DRM_SAM_MAPQ: ref_len " + std::to_string(ref_len) + " outside [1, 2^20]");
+    prm = drm_mapq_params{(int32_t)ref_len, (int32_t)ref_len, kMapqMinDefault, 2};
+    if (const char *mi = std::getenv("DRM_MAPQ_MIN")) {
+        long x = 0;
+        if (!parse_int(mi, x) || x > (1L << 20))
+            throw drm::Error(DRM_ERR_ARG, std::string("DRM_MAPQ_MIN must be an integer in [0, 2^20]: \"") + mi + "\"");
+        prm.min_score = (int32_t)x;
+    }
+    if (const char *sp = std::getenv("DRM_MAPQ_SPAN")) {
+        long x = 0;
+        if (!parse_int(sp, x) || x < 1 || x > (1L << 20))
+            throw drm::Error(DRM_ERR_ARG, std::string("DRM_MAPQ_SPAN must be an integer in [1, 2^20]: \"") + sp + "\"");
+        prm.locus_span = (int32_t)x;
+    }
+    if (std::getenv("DRM_SAM_L2_ROWS") && std::atoi(std::getenv("DRM_SAM_L2_ROWS")) != 0)
+        throw drm::Error(DRM_ERR_ARG, "DRM_SAM_MAPQ does not go with DRM_SAM_L2_ROWS=1: those rows carry distances, "
+                                      "not scores");
+    return true;
+}
+
+// a read's self score under the rerank's scoring: its length without format_fastq's tags
+static int32_t untagged_length(const std::string &tagged)
+{
+    const int pre = !tagged.empty() && tagged.front() == '<', post = tagged.size() > 1 && tagged.back() == '>';
+    return (int32_t)tagged.size() - pre - post;
+}
+
 // DRM_PAIR_RESCUE=1, one block of pairs after drm_pair_hits: pair p's reads are the block's queries 2p and 2p + 1, their
 // rerank lists ids / scores [2 * npairs][k]. A pair of status 1 gives two tasks (mate 2 against the insert window of
 // mate 1's chosen hit, then mate 1 against that of mate 2's), status 2 / 3 one; drm_mate_rescue scores them with the
 // rerank's scoring and drm_pair_rescue_choose decides. A rescued mate's window id goes where its chosen row's id
-// would be in the list handed to the aligner, and its pair counts as proper.
+// would be in the list handed to the aligner, and its pair counts as proper. `after` / `rescue_score` (DRM_SAM_MAPQ,
+// null otherwise) receive a rescued pair's record and the rescued mate's own score.
 static void rescue_block(drm_refs *rt, const PairMode &mode, int64_t glen, const std::vector<drm_pair_result> &res,
                          const uint64_t *ids, const int32_t *scores, size_t k, const uint8_t *queries,
                          const int32_t *q_len, int32_t q_stride, std::vector<uint64_t> &chosen,
-                         std::vector<int32_t> &cnt, std::vector<int32_t> &proper)
+                         std::vector<int32_t> &cnt, std::vector<int32_t> &proper,
+                         std::vector<drm_pair_result> *after = nullptr, std::vector<int32_t> *rescue_score = nullptr)
 {
     const size_t np = res.size();
     auto row_id = [&](size_t read, int32_t j) { return j >= 0 ? ids[read * k + (size_t)j] : (uint64_t)0; };
@@ -306,6 +349,10 @@ static void rescue_block(drm_refs *rt, const PairMode &mode, int64_t glen, const
         chosen[read] = wr;
         cnt[read] = 1;
         proper[p] = 1;
+        if (after) {
+            (*after)[p] = r;
+            (*rescue_score)[p] = (r.status == 5 ? rA : rB)->score;
+        }
     }
 }
 
@@ -354,6 +401,9 @@ int main(int argc, char *argv[])
         const AffineMode *affine = cigar_env && affine_mode_from_env(ref_len, affine_mode) ? &affine_mode : nullptr;
         PairMode pair_mode{};
         const bool paired = pair_mode_from_env(ref_len, pair_mode);
+        drm_mapq_params mapq_prm{};
+        const bool mapq_on = use_dynamic && use_streaming && cigar_env &&
+                             std::filesystem::path(argv[2]).extension() != ".npy" && mapq_mode_from_env(ref_len, mapq_prm);
         if (paired) {
             if (!use_dynamic || !use_streaming)
                 throw drm::Error(DRM_ERR_ARG, "DRM_MATES needs use_dynamic=1 and use_streaming=1: pairs are written to the "
@@ -383,6 +433,8 @@ int main(int argc, char *argv[])
         const int device = devices[0];
         if (paired && devices.size() != 1)
             throw drm::Error(DRM_ERR_UNSUPPORTED, "DRM_MATES runs on one device (DRM_DEVICE), not on DRM_DEVICES");
+        if (mapq_on && devices.size() != 1)
+            throw drm::Error(DRM_ERR_UNSUPPORTED, "DRM_SAM_MAPQ runs on one device (DRM_DEVICE), not on DRM_DEVICES");
 
         // ---- data loading
         std::vector<float> emb;
@@ -571,10 +623,10 @@ int main(int argc, char *argv[])
         // reranker meant to write: the L2 rows of every query, and none for a query whose
         // candidate range runs past the clipped expansion stream (the reference reads out of bounds there).
         const bool stream_sam = use_streaming && dyn;
-        // DRM_MATES: pairing needs scores, so the SW rerank runs whatever the stride
-        const bool sam_from_search = stream_sam && stride == 1 && !paired;
+        // DRM_MATES, DRM_SAM_MAPQ: pairing and MAPQ need scores, so the SW rerank runs whatever the stride
+        const bool sam_from_search = stream_sam && stride == 1 && !paired && !mapq_on;
         const bool l2_rows = std::getenv("DRM_SAM_L2_ROWS") && std::atoi(std::getenv("DRM_SAM_L2_ROWS")) != 0;
-        const bool sam_header_only = stream_sam && stride > 1 && !l2_rows && !paired;
+        const bool sam_header_only = stream_sam && stride > 1 && !l2_rows && !paired && !mapq_on;
         // DRM_SAM_CIGAR=1: every SAM row gets its real POS / CIGAR / AS / NM from a GPU
         // alignment of the block's rows (drm_sw_align) before the host thread formats the block. Unset: no
         // alignment is launched and the file is the reference's.
@@ -689,6 +741,7 @@ int main(int argc, char *argv[])
                 auto ids = std::make_shared<std::vector<uint64_t>>(m, 0);
                 auto cnt = std::make_shared<std::vector<int32_t>>(m, 0);
                 auto proper = std::make_shared<std::vector<int32_t>>(mp, 0);
+                auto line_mapq = std::make_shared<std::vector<int32_t>>(mapq_on ? m : 0, 0);
                 auto ba = std::make_shared<BlockAlignments>();
                 if (rc == DRM_OK) {
                     try {
@@ -707,9 +760,31 @@ int main(int argc, char *argv[])
                                 }
                             (*proper)[p] = res[p].status == 0;
                         }
+                        // DRM_SAM_MAPQ: the pair MAPQ of the same lists, before a rescue changes the choice
+                        std::vector<drm_pair_mapq_result> pm(mapq_on ? mp : 0);
+                        std::vector<int32_t> full(mapq_on ? m : 0), rescue_score(mapq_on ? mp : 0, 0);
+                        std::vector<drm_pair_result> after;
+                        if (mapq_on) {
+                            for (size_t r = 0; r < m; ++r)
+                                full[r] = untagged_length(qseqs[lo + r]);
+                            check(drm_pair_mapq(&pair_mode.prm, &mapq_prm, sw_ids.p + at, sw_scores.p + at, status.p + lo,
+                                                sw_ids.p + at + k, sw_scores.p + at + k, status.p + lo + 1, full.data(),
+                                                full.data() + 1, res.data(), (int64_t)mp, k, 2, pm.data()));
+                            after = res;
+                        }
                         if (pair_mode.rescue)
                             rescue_block(art, pair_mode, (int64_t)genome.size(), res, sw_ids.p + at, sw_scores.p + at,
-                                         (size_t)k, qbuf.p + lo * qs, ql.p + lo, (int32_t)qs, *ids, *cnt, *proper);
+                                         (size_t)k, qbuf.p + lo * qs, ql.p + lo, (int32_t)qs, *ids, *cnt, *proper,
+                                         mapq_on ? &after : nullptr, mapq_on ? &rescue_score : nullptr);
+                        if (mapq_on) {
+                            if (pair_mode.rescue)
+                                check(drm_pair_mapq_rescued(&mapq_prm, after.data(), rescue_score.data(), full.data(),
+                                                            full.data() + 1, (int64_t)mp, 2, pm.data()));
+                            for (size_t p = 0; p < mp; ++p) {
+                                (*line_mapq)[2 * p] = pm[p].mapq1;
+                                (*line_mapq)[2 * p + 1] = pm[p].mapq2;
+                            }
+                        }
                         ba->align(art, ids->data(), cnt->data(), m, 1, qbuf.p + lo * qs, ql.p + lo, (int32_t)qs,
                                   (int32_t)ref_len, affine);
                     } catch (...) {
@@ -721,10 +796,11 @@ int main(int argc, char *argv[])
                 if (writer.joinable())
                     writer.join();
                 if (rc == DRM_OK && werr.empty())
-                    writer = std::thread([&, lo, mp, ids, cnt, proper, ba] {
+                    writer = std::thread([&, lo, mp, ids, cnt, proper, ba, line_mapq] {
                         try {
                             drm::write_sam_pairs(sam_file, lo == 0, "ref", ref_len, qseqs, qids, lo, mp, ids->data(),
-                                                 cnt->data(), proper->data(), ba->view());
+                                                 cnt->data(), proper->data(), ba->view(),
+                                                 mapq_on ? line_mapq->data() : nullptr);
                         } catch (const std::exception &e) {
                             werr = e.what();
                         }
@@ -757,12 +833,24 @@ int main(int argc, char *argv[])
                 const uint64_t *rows = sam_from_search ? reinterpret_cast<const uint64_t *>(I.p) + lo * k_clusters
                                                        : sw_ids.p + lo * k;
                 auto cnt = std::make_shared<std::vector<int32_t>>(m);
+                auto line_mapq = std::make_shared<std::vector<int32_t>>(mapq_on ? m * kr : 0, 0);
                 auto ba = std::make_shared<BlockAlignments>();
                 if (rc == DRM_OK) {
                     for (size_t i = 0; i < m; ++i)
                         (*cnt)[i] = sam_from_search ? std::min(k, k_clusters) : std::max(status.p[lo + i], 0);
                     if (sam_cigar) {
                         try {
+                            if (mapq_on) { // DRM_SAM_MAPQ: the locus scan of the block's rerank rows, head = the primary row
+                                std::vector<int32_t> full(m), head(m, 0);
+                                std::vector<drm_mapq_result> res(m);
+                                for (size_t i = 0; i < m; ++i)
+                                    full[i] = untagged_length(qseqs[lo + i]);
+                                check(drm_set_device(device));
+                                check(drm_hit_mapq(&mapq_prm, rows, sw_scores.p + lo * k, status.p + lo, head.data(),
+                                                   full.data(), (int64_t)m, k, res.data()));
+                                for (size_t i = 0; i < m; ++i)
+                                    (*line_mapq)[i * kr] = res[i].mapq; // secondary lines print 0
+                            }
                             ba->align(art, rows, cnt->data(), m, kr, qbuf.p + lo * qs, ql.p + lo, (int32_t)qs,
                                       (int32_t)ref_len, affine);
                         } catch (...) {
@@ -775,11 +863,12 @@ int main(int argc, char *argv[])
                 if (writer.joinable())
                     writer.join();
                 if (rc == DRM_OK && werr.empty())
-                    writer = std::thread([&, lo, m, kr, rows, cnt, ba] {
+                    writer = std::thread([&, lo, m, kr, rows, cnt, ba, line_mapq] {
                         try {
                             const drm::SamAlignments av = ba->view();
                             drm::write_sam_block(sam_file, lo == 0, "ref", ref_len, qseqs, qids, lo, m, rows,
-                                                 cnt->data(), kr, sam_cigar ? &av : nullptr);
+                                                 cnt->data(), kr, sam_cigar ? &av : nullptr,
+                                                 mapq_on ? line_mapq->data() : nullptr);
                         } catch (const std::exception &e) {
                             werr = e.what();
                         }
