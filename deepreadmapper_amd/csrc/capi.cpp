@@ -63,7 +63,7 @@ template <class T> struct DevBuf { // RAII device buffer for host-pointer entry 
         if (p)
             (void)hipFree(p);
     }
-    DevBuf(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; }
     DevBuf &operator=(const DevBuf &) = delete;
     void upload(const T *h) { DRM_HIP_CHECK(hipMemcpy(p, h, sizeof(T) * n, hipMemcpyHostToDevice)); }
     void download(T *h) const { DRM_HIP_CHECK(hipMemcpy(h, p, sizeof(T) * n, hipMemcpyDeviceToHost)); }
@@ -1670,24 +1670,51 @@ static drm::AlignArgs make_align_args(const drm_refs *refs, const uint64_t *ids,
         throw Error(DRM_ERR_ARG, "null refs");
     if (npairs < 0 || nq < 0 || q_stride < 0 || ops_stride < 0)
         throw Error(DRM_ERR_ARG, "negative npairs / nq / q_stride / ops_stride");
-    drm::AlignArgs a{};
-    a.refs = refs->dev.windows;
-    a.n_ref = refs->dev.genome ? 0 : refs->dev.n_ref;
-    a.ref_len = refs->dev.ref_len;
-    a.row_stride = refs->dev.row_stride;
-    a.genome = refs->dev.genome;
-    a.glen = refs->dev.glen;
-    a.window_ids = ids;
-    a.pair_query = pq;
-    a.npairs = npairs;
-    a.queries = q;
-    a.q_len = ql;
-    a.q_stride = q_stride;
-    a.nq = nq;
-    a.out = out;
-    a.ops = ops;
-    a.ops_stride = ops_stride;
-    return a;
+    const drm::DeviceRefs &d = refs->dev;
+    return drm::AlignArgs{d.windows, d.genome ? 0 : d.n_ref, d.ref_len, d.row_stride, d.genome, d.glen, ids, pq,
+                          npairs, q, ql, q_stride, nq, out, ops, ops_stride};
+}
+
+// the pointers a non-empty list of pairs (alignment) or tasks (mate rescue) needs, host or device form alike; the
+// rescue writes no operation words
+static void require_list_pointers(const void *ids, const void *query_of, const void *out, int64_t nq, const void *queries,
+                                  const void *q_len, const void *ops = nullptr, int32_t ops_stride = 0)
+{
+    if (!ids || !query_of || !out || (!ops && ops_stride > 0) || (nq > 0 && (!queries || !q_len)))
+        throw Error(DRM_ERR_ARG, "null argument");
+}
+
+// The host form's inputs for such a list of n `what`s ("pair", "task"): every q_len[] within [0, q_stride], every
+// query_of[] within [0, nq), then `device` made current and the list, the query bytes and their lengths uploaded.
+struct ListUpload {
+    DevBuf<uint64_t> ids;
+    DevBuf<int64_t> query_of;
+    DevBuf<uint8_t> queries;
+    DevBuf<int32_t> q_len;
+    int longest; // the largest q_len
+};
+static ListUpload upload_list(int device, const char *what, const uint64_t *ids, const int64_t *query_of, int64_t n,
+                              const uint8_t *queries, const int32_t *q_len, int32_t q_stride, int64_t nq)
+{
+    int max_q = 0;
+    for (int64_t i = 0; i < nq; ++i) {
+        if (q_len[i] < 0 || q_len[i] > q_stride)
+            throw Error(DRM_ERR_ARG, "query length outside [0, q_stride]");
+        max_q = std::max(max_q, q_len[i]);
+    }
+    for (int64_t p = 0; p < n; ++p)
+        if (query_of[p] < 0 || query_of[p] >= nq)
+            throw Error(DRM_ERR_ARG, std::string(what) + " " + std::to_string(p) + " names query " +
+                                         std::to_string(query_of[p]) + " outside [0, " + std::to_string(nq) + ")");
+    DRM_HIP_CHECK(hipSetDevice(device));
+    ListUpload u{DevBuf<uint64_t>((size_t)n), DevBuf<int64_t>((size_t)n), DevBuf<uint8_t>((size_t)nq * (size_t)q_stride),
+                 DevBuf<int32_t>((size_t)nq), max_q};
+    u.ids.upload(ids);
+    u.query_of.upload(query_of);
+    if (u.queries.n)
+        u.queries.upload(queries);
+    u.q_len.upload(q_len);
+    return u;
 }
 
 int drm_sw_align_device(drm_refs *refs, const uint64_t *d_window_ids, const int64_t *d_pair_query, int64_t npairs,
@@ -1699,8 +1726,7 @@ int drm_sw_align_device(drm_refs *refs, const uint64_t *d_window_ids, const int6
                                            d_out, d_ops, ops_stride);
         if (npairs == 0)
             return;
-        if (!d_window_ids || !d_pair_query || !d_out || (!d_ops && ops_stride > 0) || (nq > 0 && (!d_queries || !d_q_len)))
-            throw Error(DRM_ERR_ARG, "null argument");
+        require_list_pointers(d_window_ids, d_pair_query, d_out, nq, d_queries, d_q_len, d_ops, ops_stride);
         DRM_HIP_CHECK(hipSetDevice(refs->dev.device));
         // max query length bounded by the row stride of the query buffer
         drm::launch_sw_align(refs->dev, a, q_stride, (hipStream_t)stream);
@@ -1717,39 +1743,20 @@ static void sw_align_host(drm_refs *refs, const uint64_t *window_ids, const int6
                                        nullptr, ops_stride);
     if (npairs == 0)
         return;
-    if (!window_ids || !pair_query || !out || (!ops && ops_stride > 0) || (nq > 0 && (!queries || !q_len)))
-        throw Error(DRM_ERR_ARG, "null argument");
-    int max_q = 0;
-    for (int64_t i = 0; i < nq; ++i) {
-        if (q_len[i] < 0 || q_len[i] > q_stride)
-            throw Error(DRM_ERR_ARG, "query length outside [0, q_stride]");
-        max_q = std::max(max_q, q_len[i]);
-    }
-    for (int64_t p = 0; p < npairs; ++p)
-        if (pair_query[p] < 0 || pair_query[p] >= nq)
-            throw Error(DRM_ERR_ARG, "pair " + std::to_string(p) + " names query " + std::to_string(pair_query[p]) +
-                                         " outside [0, " + std::to_string(nq) + ")");
-    DRM_HIP_CHECK(hipSetDevice(refs->dev.device));
-    DevBuf<uint64_t> di((size_t)npairs);
-    DevBuf<int64_t> dp((size_t)npairs);
-    DevBuf<uint8_t> dq((size_t)nq * (size_t)q_stride);
-    DevBuf<int32_t> dl((size_t)nq);
+    require_list_pointers(window_ids, pair_query, out, nq, queries, q_len, ops, ops_stride);
+    const ListUpload in =
+        upload_list(refs->dev.device, "pair", window_ids, pair_query, npairs, queries, q_len, q_stride, nq);
     DevBuf<drm_sw_alignment> dout((size_t)npairs);
     DevBuf<uint32_t> dops((size_t)npairs * (size_t)ops_stride);
-    di.upload(window_ids);
-    dp.upload(pair_query);
-    if (dq.n)
-        dq.upload(queries);
-    dl.upload(q_len);
     if (dops.n) // words past a pair's n_ops read as 0
         DRM_HIP_CHECK(hipMemset(dops.p, 0, sizeof(uint32_t) * dops.n));
-    a.window_ids = di.p;
-    a.pair_query = dp.p;
-    a.queries = dq.p;
-    a.q_len = dl.p;
+    a.window_ids = in.ids.p;
+    a.pair_query = in.query_of.p;
+    a.queries = in.queries.p;
+    a.q_len = in.q_len.p;
     a.out = dout.p;
     a.ops = dops.p;
-    launch(a, max_q);
+    launch(a, in.longest);
     DRM_HIP_CHECK(hipDeviceSynchronize());
     dout.download(out);
     if (dops.n)
@@ -1767,25 +1774,11 @@ int drm_sw_align(drm_refs *refs, const uint64_t *window_ids, const int64_t *pair
 }
 
 // ---------------------------------------------------------------------- affine-gap alignment (sw_align_affine.hip)
-// drm_sw_scoring's accepted ranges (drm_sw_align_affine, drm_mate_rescue)
-static void check_scoring(const drm_sw_scoring *sc)
-{
-    auto range = [](const char *name, int32_t v, int32_t lo, int32_t hi) {
-        if (v < lo || v > hi)
-            throw Error(DRM_ERR_ARG, std::string("scoring: ") + name + " " + std::to_string(v) + " outside [" +
-                                         std::to_string(lo) + ", " + std::to_string(hi) + "]");
-    };
-    range("match", sc->match, 1, 31);
-    range("mismatch", sc->mismatch, 1, 63);
-    range("gap_open", sc->gap_open, 0, 63);
-    range("gap_extend", sc->gap_extend, 1, 63);
-}
-
 static drm::AffineAlignArgs make_affine_args(const drm_refs *refs, const drm_sw_scoring *sc, int32_t flank)
 {
     if (!refs || !sc)
         throw Error(DRM_ERR_ARG, "null refs / scoring");
-    check_scoring(sc);
+    drm::check_scoring(sc);
     if (flank < 0)
         throw Error(DRM_ERR_ARG, "negative flank");
     if (flank > 0 && !refs->dev.genome)
@@ -1794,13 +1787,7 @@ static drm::AffineAlignArgs make_affine_args(const drm_refs *refs, const drm_sw_
         throw Error(DRM_ERR_UNSUPPORTED, "window length " + std::to_string(refs->dev.ref_len) + " + 2 * flank " +
                                              std::to_string(flank) +
                                              " > 256 is not supported by the GPU affine SW alignment kernel");
-    drm::AffineAlignArgs aa{};
-    aa.match = sc->match;
-    aa.mismatch = sc->mismatch;
-    aa.gap_open = sc->gap_open;
-    aa.gap_extend = sc->gap_extend;
-    aa.flank = flank;
-    return aa;
+    return drm::AffineAlignArgs{{}, sc->match, sc->mismatch, sc->gap_open, sc->gap_extend, flank, 0};
 }
 
 int drm_sw_align_affine_device(drm_refs *refs, const drm_sw_scoring *scoring, int32_t flank,
@@ -1814,8 +1801,7 @@ int drm_sw_align_affine_device(drm_refs *refs, const drm_sw_scoring *scoring, in
                                   d_ops, ops_stride);
         if (npairs == 0)
             return;
-        if (!d_window_ids || !d_pair_query || !d_out || (!d_ops && ops_stride > 0) || (nq > 0 && (!d_queries || !d_q_len)))
-            throw Error(DRM_ERR_ARG, "null argument");
+        require_list_pointers(d_window_ids, d_pair_query, d_out, nq, d_queries, d_q_len, d_ops, ops_stride);
         DRM_HIP_CHECK(hipSetDevice(refs->dev.device));
         drm::launch_sw_align_affine(refs->dev, aa, q_stride, (hipStream_t)stream);
     });
@@ -1847,7 +1833,7 @@ int drm_sw_align_region(const drm_refs *refs, uint64_t window_id, int32_t flank,
             throw Error(DRM_ERR_ARG, "negative flank");
         if ((int64_t)refs->dev.ref_len + 2 * (int64_t)flank > drm::kAlignMaxLen)
             throw Error(DRM_ERR_UNSUPPORTED, "window length + 2 * flank > 256");
-        const uint64_t pos = window_id >> 1;
+        const uint64_t pos = window_id >> 1; // the twin of sw_align_affine_kernel's region (sw_align_affine.hip)
         *reverse = (int32_t)(window_id & 1u);
         *start = 0;
         *len = 0;
@@ -1864,25 +1850,63 @@ int drm_sw_align_region(const drm_refs *refs, uint64_t window_id, int32_t flank,
 static drm::PairArgs make_pair_args(const drm_pair_params *p, const uint64_t *ids1, const int32_t *scores1,
                                     const int32_t *cnt1, const uint64_t *ids2, const int32_t *scores2,
                                     const int32_t *cnt2, int64_t npairs, int32_t k, int64_t row_step,
-                                    drm_pair_result *out)
+                                    drm_pair_result *out, bool need_out = true)
 {
     if (!p)
         throw Error(DRM_ERR_ARG, "null pair parameters");
     if (k < 0 || k > drm::kMaxCands)
         throw Error(DRM_ERR_UNSUPPORTED, "k = " + std::to_string(k) + " outside [0, 1024], the rerank's candidate cap");
-    if (p->ref_len < 1 || p->ref_len > (1 << 20))
-        throw Error(DRM_ERR_ARG, "ref_len " + std::to_string(p->ref_len) + " outside [1, 2^20]");
-    if (p->min_tlen < 0 || p->min_tlen > p->max_tlen || p->max_tlen > (1 << 30))
-        throw Error(DRM_ERR_ARG, "template lengths [" + std::to_string(p->min_tlen) + ", " +
-                                     std::to_string(p->max_tlen) + "] must satisfy 0 <= min <= max <= 2^30");
+    drm::check_pair_params(p);
     if (p->unpaired_penalty < 0 || p->unpaired_penalty > (1 << 20))
         throw Error(DRM_ERR_ARG, "unpaired_penalty " + std::to_string(p->unpaired_penalty) + " outside [0, 2^20]");
     if (npairs < 0 || row_step < 1)
         throw Error(DRM_ERR_ARG, "npairs must be >= 0 and row_step >= 1");
-    if (npairs > 0 && (!cnt1 || !cnt2 || !out || (k > 0 && (!ids1 || !scores1 || !ids2 || !scores2))))
+    if (npairs > 0 && (!cnt1 || !cnt2 || (need_out && !out) || (k > 0 && (!ids1 || !scores1 || !ids2 || !scores2))))
         throw Error(DRM_ERR_ARG, "null argument");
     return drm::PairArgs{*p, ids1, scores1, cnt1, ids2, scores2, cnt2, npairs, k, row_step, out};
 }
+
+// the counted rows' scores of `n` lists `step` rows apart, before anything reaches the device; list q is named
+// `before` q `after` in the message
+static void check_list_scores(const int32_t *cnt, const int32_t *sc, int64_t n, int64_t step, int32_t k,
+                              const char *before, const char *after = "")
+{
+    for (int64_t q = 0; q < n; ++q) {
+        const int64_t row = q * step;
+        const int32_t c = std::min(std::max(cnt[row], 0), k);
+        for (int32_t j = 0; j < c; ++j)
+            if (sc[row * k + j] < 0 || sc[row * k + j] > (1 << 20))
+                throw Error(DRM_ERR_ARG, before + std::to_string(q) + after + ", row " + std::to_string(j) + ": score " +
+                                             std::to_string(sc[row * k + j]) + " outside [0, 2^20]");
+    }
+}
+
+// One read's or one mate's hit lists on the device, for the host-pointer entry points: ids and scores [rows][k],
+// counts [rows] and, where the call has them, the self scores full [rows]. The lists of `n` pairs `step` rows apart
+// span list_rows(n, step) rows from the mate's own base pointer (the two mates' may overlap).
+static size_t list_rows(int64_t n, int64_t step) { return (size_t)(n - 1) * (size_t)step + 1; }
+struct HitLists {
+    DevBuf<uint64_t> ids;
+    DevBuf<int32_t> scores, cnt, full;
+    HitLists(const uint64_t *h_ids, const int32_t *h_scores, const int32_t *h_cnt, const int32_t *h_full, size_t rows,
+             int32_t k)
+        : ids(rows * (size_t)k), scores(rows * (size_t)k), cnt(rows), full(h_full ? rows : 0)
+    {
+        if (k > 0) {
+            ids.upload(h_ids);
+            scores.upload(h_scores);
+        }
+        cnt.upload(h_cnt);
+        if (h_full)
+            full.upload(h_full);
+    }
+    void bind(const uint64_t *&a_ids, const int32_t *&a_scores, const int32_t *&a_cnt) const
+    {
+        a_ids = ids.p;
+        a_scores = scores.p;
+        a_cnt = cnt.p;
+    }
+};
 
 int drm_pair_hits_device(const drm_pair_params *p, const uint64_t *d_ids1, const int32_t *d_scores1,
                          const int32_t *d_cnt1, const uint64_t *d_ids2, const int32_t *d_scores2,
@@ -1904,38 +1928,13 @@ int drm_pair_hits(const drm_pair_params *p, const uint64_t *ids1, const int32_t 
         drm::PairArgs a = make_pair_args(p, ids1, scores1, cnt1, ids2, scores2, cnt2, npairs, k, row_step, out);
         if (npairs == 0)
             return;
-        // the counted rows' scores, before anything reaches the device
-        for (int m = 0; m < 2; ++m) {
-            const int32_t *cnt = m ? cnt2 : cnt1, *sc = m ? scores2 : scores1;
-            for (int64_t q = 0; q < npairs; ++q) {
-                const int64_t row = q * row_step;
-                const int32_t c = std::min(std::max(cnt[row], 0), k);
-                for (int32_t j = 0; j < c; ++j)
-                    if (sc[row * k + j] < 0 || sc[row * k + j] > (1 << 20))
-                        throw Error(DRM_ERR_ARG, "pair " + std::to_string(q) + ", mate " + std::to_string(m + 1) +
-                                                     ", row " + std::to_string(j) + ": score " +
-                                                     std::to_string(sc[row * k + j]) + " outside [0, 2^20]");
-            }
-        }
-        // each mate's lists span ((npairs - 1) * row_step + 1) rows from its own base pointer (the two may overlap)
-        const size_t rows = (size_t)(npairs - 1) * (size_t)row_step + 1;
-        DevBuf<uint64_t> di1(rows * (size_t)k), di2(rows * (size_t)k);
-        DevBuf<int32_t> ds1(rows * (size_t)k), ds2(rows * (size_t)k), dc1(rows), dc2(rows);
+        check_list_scores(cnt1, scores1, npairs, row_step, k, "pair ", ", mate 1");
+        check_list_scores(cnt2, scores2, npairs, row_step, k, "pair ", ", mate 2");
+        const size_t rows = list_rows(npairs, row_step);
+        const HitLists d1(ids1, scores1, cnt1, nullptr, rows, k), d2(ids2, scores2, cnt2, nullptr, rows, k);
         DevBuf<drm_pair_result> dout((size_t)npairs);
-        if (k > 0) {
-            di1.upload(ids1);
-            di2.upload(ids2);
-            ds1.upload(scores1);
-            ds2.upload(scores2);
-        }
-        dc1.upload(cnt1);
-        dc2.upload(cnt2);
-        a.ids1 = di1.p;
-        a.ids2 = di2.p;
-        a.scores1 = ds1.p;
-        a.scores2 = ds2.p;
-        a.cnt1 = dc1.p;
-        a.cnt2 = dc2.p;
+        d1.bind(a.ids1, a.scores1, a.cnt1);
+        d2.bind(a.ids2, a.scores2, a.cnt2);
         a.out = dout.p;
         drm::launch_pair_hits(a, nullptr);
         DRM_HIP_CHECK(hipDeviceSynchronize());
@@ -1958,19 +1957,6 @@ static drm::MapqArgs make_mapq_args(const drm_mapq_params *p, const uint64_t *id
     return drm::MapqArgs{*p, ids, scores, cnt, head, full, nreads, k, out};
 }
 
-// the counted rows' scores of `n` lists `step` rows apart, before anything reaches the device
-static void check_list_scores(const int32_t *cnt, const int32_t *sc, int64_t n, int64_t step, int32_t k, const char *what)
-{
-    for (int64_t q = 0; q < n; ++q) {
-        const int64_t row = q * step;
-        const int32_t c = std::min(std::max(cnt[row], 0), k);
-        for (int32_t j = 0; j < c; ++j)
-            if (sc[row * k + j] < 0 || sc[row * k + j] > (1 << 20))
-                throw Error(DRM_ERR_ARG, std::string(what) + " " + std::to_string(q) + ", row " + std::to_string(j) +
-                                             ": score " + std::to_string(sc[row * k + j]) + " outside [0, 2^20]");
-    }
-}
-
 int drm_hit_mapq_device(const drm_mapq_params *p, const uint64_t *d_ids, const int32_t *d_scores, const int32_t *d_cnt,
                         const int32_t *d_head, const int32_t *d_full, int64_t nreads, int32_t k,
                         drm_mapq_result *d_out, void *stream)
@@ -1988,24 +1974,15 @@ int drm_hit_mapq(const drm_mapq_params *p, const uint64_t *ids, const int32_t *s
         drm::MapqArgs a = make_mapq_args(p, ids, scores, cnt, head, full, nreads, k, out);
         if (nreads == 0)
             return;
-        check_list_scores(cnt, scores, nreads, 1, k, "read");
-        DevBuf<uint64_t> di((size_t)nreads * (size_t)k);
-        DevBuf<int32_t> ds((size_t)nreads * (size_t)k), dc((size_t)nreads), dh(head ? (size_t)nreads : 0),
-            df((size_t)nreads);
+        check_list_scores(cnt, scores, nreads, 1, k, "read ");
+        const HitLists d(ids, scores, cnt, full, (size_t)nreads, k);
+        DevBuf<int32_t> dh(head ? (size_t)nreads : 0);
         DevBuf<drm_mapq_result> dout((size_t)nreads);
-        if (k > 0) {
-            di.upload(ids);
-            ds.upload(scores);
-        }
-        dc.upload(cnt);
-        df.upload(full);
         if (head)
             dh.upload(head);
-        a.ids = di.p;
-        a.scores = ds.p;
-        a.cnt = dc.p;
-        a.head = head ? dh.p : nullptr;
-        a.full = df.p;
+        d.bind(a.ids, a.scores, a.cnt);
+        a.head = dh.p;
+        a.full = d.full.p;
         a.out = dout.p;
         drm::launch_hit_mapq(a, nullptr);
         DRM_HIP_CHECK(hipDeviceSynchronize());
@@ -2020,10 +1997,9 @@ int drm_pair_mapq_device(const drm_pair_params *pp, const drm_mapq_params *mp, c
                          int64_t row_step, drm_pair_mapq_result *d_out, void *stream)
 {
     return guarded([&] {
-        drm_pair_result unused{};
         drm::PairMapqArgs a{};
-        a.pair = make_pair_args(pp, d_ids1, d_scores1, d_cnt1, d_ids2, d_scores2, d_cnt2, npairs, k, row_step, &unused);
-        a.pair.out = nullptr;
+        a.pair = make_pair_args(pp, d_ids1, d_scores1, d_cnt1, d_ids2, d_scores2, d_cnt2, npairs, k, row_step, nullptr,
+                                false);
         drm::check_mapq_params(mp);
         if (npairs > 0 && (!d_full1 || !d_full2 || !d_pairs || !d_out))
             throw Error(DRM_ERR_ARG, "null argument");
@@ -2042,10 +2018,8 @@ int drm_pair_mapq(const drm_pair_params *pp, const drm_mapq_params *mp, const ui
                   int64_t row_step, drm_pair_mapq_result *out)
 {
     return guarded([&] {
-        drm_pair_result unused{};
         drm::PairMapqArgs a{};
-        a.pair = make_pair_args(pp, ids1, scores1, cnt1, ids2, scores2, cnt2, npairs, k, row_step, &unused);
-        a.pair.out = nullptr;
+        a.pair = make_pair_args(pp, ids1, scores1, cnt1, ids2, scores2, cnt2, npairs, k, row_step, nullptr, false);
         drm::check_mapq_params(mp);
         if (npairs > 0 && (!full1 || !full2 || !pairs || !out))
             throw Error(DRM_ERR_ARG, "null argument");
@@ -2055,34 +2029,18 @@ int drm_pair_mapq(const drm_pair_params *pp, const drm_mapq_params *mp, const ui
             if (pairs[q].status < 0 || pairs[q].status > 4)
                 throw Error(DRM_ERR_ARG, "pair " + std::to_string(q) + ": status " + std::to_string(pairs[q].status) +
                                              " outside [0, 4]");
-        check_list_scores(cnt1, scores1, npairs, row_step, k, "mate 1 of pair");
-        check_list_scores(cnt2, scores2, npairs, row_step, k, "mate 2 of pair");
-        // each mate's lists span ((npairs - 1) * row_step + 1) rows from its own base pointer (the two may overlap)
-        const size_t rows = (size_t)(npairs - 1) * (size_t)row_step + 1;
-        DevBuf<uint64_t> di1(rows * (size_t)k), di2(rows * (size_t)k);
-        DevBuf<int32_t> ds1(rows * (size_t)k), ds2(rows * (size_t)k), dc1(rows), dc2(rows), df1(rows), df2(rows);
+        check_list_scores(cnt1, scores1, npairs, row_step, k, "mate 1 of pair ");
+        check_list_scores(cnt2, scores2, npairs, row_step, k, "mate 2 of pair ");
+        const size_t rows = list_rows(npairs, row_step);
+        const HitLists d1(ids1, scores1, cnt1, full1, rows, k), d2(ids2, scores2, cnt2, full2, rows, k);
         DevBuf<drm_pair_result> dp((size_t)npairs);
         DevBuf<drm_pair_mapq_result> dout((size_t)npairs);
-        if (k > 0) {
-            di1.upload(ids1);
-            di2.upload(ids2);
-            ds1.upload(scores1);
-            ds2.upload(scores2);
-        }
-        dc1.upload(cnt1);
-        dc2.upload(cnt2);
-        df1.upload(full1);
-        df2.upload(full2);
         dp.upload(pairs);
-        a.pair.ids1 = di1.p;
-        a.pair.ids2 = di2.p;
-        a.pair.scores1 = ds1.p;
-        a.pair.scores2 = ds2.p;
-        a.pair.cnt1 = dc1.p;
-        a.pair.cnt2 = dc2.p;
+        d1.bind(a.pair.ids1, a.pair.scores1, a.pair.cnt1);
+        d2.bind(a.pair.ids2, a.pair.scores2, a.pair.cnt2);
         a.prm = *mp;
-        a.full1 = df1.p;
-        a.full2 = df2.p;
+        a.full1 = d1.full.p;
+        a.full2 = d2.full.p;
         a.pairs = dp.p;
         a.out = dout.p;
         drm::launch_pair_mapq(a, nullptr);
@@ -2100,30 +2058,16 @@ static drm::RescueArgs make_rescue_args(const drm_refs *refs, const drm_sw_scori
         throw Error(DRM_ERR_ARG, "null refs / scoring / pair parameters");
     if (!refs->dev.genome)
         throw Error(DRM_ERR_ARG, "mate rescue needs a genome handle: a window table holds nothing between its rows");
-    check_scoring(sc);
-    drm::RescueArgs a{};
-    drm::check_rescue_params(p, a.dlo, a.dhi);
+    drm::check_scoring(sc);
+    int64_t dlo = 0, dhi = 0;
+    drm::check_rescue_params(p, dlo, dhi);
     if (p->ref_len != refs->dev.ref_len)
         throw Error(DRM_ERR_ARG, "the pair parameters' ref_len " + std::to_string(p->ref_len) + " is not the handle's " +
                                      std::to_string(refs->dev.ref_len));
     if (ntasks < 0 || nq < 0 || q_stride < 0)
         throw Error(DRM_ERR_ARG, "negative ntasks / nq / q_stride");
-    a.genome = refs->dev.genome;
-    a.glen = refs->dev.glen;
-    a.ref_len = p->ref_len;
-    a.match = sc->match;
-    a.mismatch = sc->mismatch;
-    a.gap_open = sc->gap_open;
-    a.gap_extend = sc->gap_extend;
-    a.anchor_ids = anchors;
-    a.task_query = tq;
-    a.ntasks = ntasks;
-    a.queries = q;
-    a.q_len = ql;
-    a.q_stride = q_stride;
-    a.nq = nq;
-    a.out = out;
-    return a;
+    return drm::RescueArgs{refs->dev.genome, refs->dev.glen, p->ref_len, dlo, dhi, sc->match, sc->mismatch, sc->gap_open,
+                           sc->gap_extend, anchors, tq, ntasks, q, ql, q_stride, nq, out};
 }
 
 int drm_mate_rescue_device(drm_refs *refs, const drm_sw_scoring *scoring, const drm_pair_params *p,
@@ -2136,8 +2080,7 @@ int drm_mate_rescue_device(drm_refs *refs, const drm_sw_scoring *scoring, const 
                                                    d_q_len, q_stride, nq, d_out);
         if (ntasks == 0)
             return;
-        if (!d_anchor_ids || !d_task_query || !d_out || (nq > 0 && (!d_queries || !d_q_len)))
-            throw Error(DRM_ERR_ARG, "null argument");
+        require_list_pointers(d_anchor_ids, d_task_query, d_out, nq, d_queries, d_q_len);
         DRM_HIP_CHECK(hipSetDevice(refs->dev.device));
         // max query length bounded by the row stride of the query buffer
         drm::launch_mate_rescue(refs->dev.device, a, q_stride, (hipStream_t)stream);
@@ -2153,35 +2096,16 @@ int drm_mate_rescue(drm_refs *refs, const drm_sw_scoring *scoring, const drm_pai
                                              nq, nullptr);
         if (ntasks == 0)
             return;
-        if (!anchor_ids || !task_query || !out || (nq > 0 && (!queries || !q_len)))
-            throw Error(DRM_ERR_ARG, "null argument");
-        int max_q = 0;
-        for (int64_t i = 0; i < nq; ++i) {
-            if (q_len[i] < 0 || q_len[i] > q_stride)
-                throw Error(DRM_ERR_ARG, "query length outside [0, q_stride]");
-            max_q = std::max(max_q, q_len[i]);
-        }
-        for (int64_t t = 0; t < ntasks; ++t)
-            if (task_query[t] < 0 || task_query[t] >= nq)
-                throw Error(DRM_ERR_ARG, "task " + std::to_string(t) + " names query " + std::to_string(task_query[t]) +
-                                             " outside [0, " + std::to_string(nq) + ")");
-        DRM_HIP_CHECK(hipSetDevice(refs->dev.device));
-        DevBuf<uint64_t> di((size_t)ntasks);
-        DevBuf<int64_t> dt((size_t)ntasks);
-        DevBuf<uint8_t> dq((size_t)nq * (size_t)q_stride);
-        DevBuf<int32_t> dl((size_t)nq);
+        require_list_pointers(anchor_ids, task_query, out, nq, queries, q_len);
+        const ListUpload in =
+            upload_list(refs->dev.device, "task", anchor_ids, task_query, ntasks, queries, q_len, q_stride, nq);
         DevBuf<drm_rescue_result> dout((size_t)ntasks);
-        di.upload(anchor_ids);
-        dt.upload(task_query);
-        if (dq.n)
-            dq.upload(queries);
-        dl.upload(q_len);
-        a.anchor_ids = di.p;
-        a.task_query = dt.p;
-        a.queries = dq.p;
-        a.q_len = dl.p;
+        a.anchor_ids = in.ids.p;
+        a.task_query = in.query_of.p;
+        a.queries = in.queries.p;
+        a.q_len = in.q_len.p;
         a.out = dout.p;
-        drm::launch_mate_rescue(refs->dev.device, a, max_q, nullptr);
+        drm::launch_mate_rescue(refs->dev.device, a, in.longest, nullptr);
         DRM_HIP_CHECK(hipDeviceSynchronize());
         dout.download(out);
     });

@@ -438,5 +438,17 @@ __device__ __forceinline__ int wave_next_item(uint32_t *counter, int lane)
     const uint32_t old = __hip_atomic_fetch_add(counter, lane == 0 ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return __builtin_amdgcn_readfirstlane((int)old);
 }
+
+// comp_table of the reference (src/utils/parse_inputs.cpp:5-14): A<->T, C<->G, N->N, anything else 0
+__device__ __forceinline__ int comp_byte(int c)
+{
+    return c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'N' ? 'N' : 0;
+}
+
+// lane l receives lane l - 1's value, lane 0 receives `border` (DPP wave_shr:1, no source lane: the old value)
+__device__ __forceinline__ int shift_up1(int border, int x)
+{
+    return __builtin_amdgcn_update_dpp(border, x, 0x138, 0xf, 0xf, false);
+}
 } // namespace drm
 #endif

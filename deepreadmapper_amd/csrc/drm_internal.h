@@ -211,8 +211,12 @@ DRM_HOST_DEVICE inline RescueRegion rescue_region(uint64_t w, int64_t glen, int3
     r.len = (int32_t)(e - s);
     return r;
 }
-// drm_pair_hits' ranges of ref_len and the template lengths, and the rescue's row cap; returns dlo / dhi
+// drm_pair_hits' ranges of ref_len and the template lengths (DRM_ERR_ARG) ...
+void check_pair_params(const drm_pair_params *p);
+// ... and the rescue's row cap beside them; returns dlo / dhi
 void check_rescue_params(const drm_pair_params *p, int64_t &dlo, int64_t &dhi);
+// drm_sw_scoring's accepted ranges (drm_sw_align_affine, drm_mate_rescue; DRM_ERR_ARG)
+void check_scoring(const drm_sw_scoring *sc);
 
 // Mapping quality (include/drm_hip.h, drm_mapq_value): the one statement of the formula that the host entry points
 // (formats.cpp) and the kernels (mapq.hip) both compile. Arguments within [-2^20, 2^20]: 60 * 2^20 * 2^20 < 2^63.

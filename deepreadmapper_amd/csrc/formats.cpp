@@ -539,7 +539,7 @@ extern "C" int drm_sam_pair_fields(const drm_sam_mate in[2], int proper, drm_sam
 }
 
 // ----------------------------------------------------------------------- mate rescue: the host-only parts
-void drm::check_rescue_params(const drm_pair_params *p, int64_t &dlo, int64_t &dhi)
+void drm::check_pair_params(const drm_pair_params *p)
 {
     if (!p)
         throw Error(DRM_ERR_ARG, "null pair parameters");
@@ -548,6 +548,11 @@ void drm::check_rescue_params(const drm_pair_params *p, int64_t &dlo, int64_t &d
     if (p->min_tlen < 0 || p->min_tlen > p->max_tlen || p->max_tlen > (1 << 30))
         throw Error(DRM_ERR_ARG, "template lengths [" + std::to_string(p->min_tlen) + ", " +
                                      std::to_string(p->max_tlen) + "] must satisfy 0 <= min <= max <= 2^30");
+}
+
+void drm::check_rescue_params(const drm_pair_params *p, int64_t &dlo, int64_t &dhi)
+{
+    check_pair_params(p);
     dlo = std::max<int64_t>((int64_t)p->min_tlen - p->ref_len, 0);
     dhi = (int64_t)p->max_tlen - p->ref_len;
     if (dhi - dlo + p->ref_len > kRescueMaxRows)
@@ -555,6 +560,19 @@ void drm::check_rescue_params(const drm_pair_params *p, int64_t &dlo, int64_t &d
                                              std::to_string(p->max_tlen) + "] at ref_len " +
                                              std::to_string(p->ref_len) + " give a rescue region of " +
                                              std::to_string(dhi - dlo + p->ref_len) + " > 2048 rows");
+}
+
+void drm::check_scoring(const drm_sw_scoring *sc)
+{
+    auto range = [](const char *name, int32_t v, int32_t lo, int32_t hi) {
+        if (v < lo || v > hi)
+            throw Error(DRM_ERR_ARG, std::string("scoring: ") + name + " " + std::to_string(v) + " outside [" +
+                                         std::to_string(lo) + ", " + std::to_string(hi) + "]");
+    };
+    range("match", sc->match, 1, 31);
+    range("mismatch", sc->mismatch, 1, 63);
+    range("gap_open", sc->gap_open, 0, 63);
+    range("gap_extend", sc->gap_extend, 1, 63);
 }
 
 static uint64_t rescue_window(const drm_rescue_result &r, int32_t ref_len, int64_t glen)

@@ -19,18 +19,6 @@
 namespace drm {
 namespace {
 
-// comp_table of the reference (src/utils/parse_inputs.cpp:5-14): A<->T, C<->G, N->N, anything else 0
-__device__ __forceinline__ int comp_byte(int c)
-{
-    return c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'N' ? 'N' : 0;
-}
-
-// lane l receives lane l - 1's value, lane 0 receives `border` (DPP wave_shr:1, no source lane: the old value)
-__device__ __forceinline__ int shift_up1(int border, int x)
-{
-    return __builtin_amdgcn_update_dpp(border, x, 0x138, 0xf, 0xf, false);
-}
-
 constexpr int kNegInf = -(1 << 20); // the borders' E and F: below every real value, far from overflow
 
 // Best cell as one key, H << 19 | (2047 - row) << 8 | (63 - lane) << 2 | (3 - c): its maximum is the largest H, then

@@ -19,18 +19,6 @@
 namespace drm {
 namespace {
 
-// comp_table of the reference (src/utils/parse_inputs.cpp:5-14): A<->T, C<->G, N->N, anything else 0
-__device__ __forceinline__ int comp_byte(int c)
-{
-    return c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'N' ? 'N' : 0;
-}
-
-// lane l receives lane l - 1's value, lane 0 receives 0 (DPP wave_shr:1, no source lane: the old value)
-__device__ __forceinline__ int shift_up1(int x)
-{
-    return __builtin_amdgcn_update_dpp(0, x, 0x138, 0xf, 0xf, false);
-}
-
 // A cell is one signed maximum over its three candidates in the form 4 * H + priority (M 2, D 1, I 0), floored at
 // 3 = "H is 0: the walk stops": the result's upper bits are 4 * H and its low two bits are the direction, with the
 // definition's order of preference (M, then D, then I) settled by the same maximum.
@@ -122,7 +110,7 @@ __global__ __launch_bounds__(64) void sw_align_kernel(AlignArgs a)
             }
             // a lane that has not started yet still holds H = 0: the zero border above row 0
             left_prev = left_cur;
-            left_cur = shift_up1(H4[C - 1]);
+            left_cur = shift_up1(0, H4[C - 1]);
         }
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1)

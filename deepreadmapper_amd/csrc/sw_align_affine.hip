@@ -21,18 +21,6 @@
 namespace drm {
 namespace {
 
-// comp_table of the reference (src/utils/parse_inputs.cpp:5-14): A<->T, C<->G, N->N, anything else 0
-__device__ __forceinline__ int comp_byte(int c)
-{
-    return c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'N' ? 'N' : 0;
-}
-
-// lane l receives lane l - 1's value, lane 0 receives `border` (DPP wave_shr:1, no source lane: the old value)
-__device__ __forceinline__ int shift_up1(int border, int x)
-{
-    return __builtin_amdgcn_update_dpp(border, x, 0x138, 0xf, 0xf, false);
-}
-
 // Every value is kept times 4. H is one signed maximum over its candidates in the form 4 * value + priority
 // (M 2, F 1, E 0), floored at 3 = "H is 0: the walk stops", exactly as in sw_align.hip. F and E are a maximum over
 // 4 * (H - open - ext) + 1 and 4 * (F or E - ext): bit 0 of the winner says "the gap was opened here", and an equal
@@ -69,7 +57,7 @@ __global__ __launch_bounds__(64) void sw_align_affine_kernel(AffineAlignArgs aa)
         const uint8_t *wp = nullptr;
         int rc = 0, n = 0;
         if (a.genome) {
-            const uint64_t pos = wid >> 1;
+            const uint64_t pos = wid >> 1; // the twin of drm_sw_align_region (capi.cpp)
             if (pos + (uint64_t)a.ref_len <= (uint64_t)a.glen) {
                 const int64_t s = max((int64_t)pos - aa.flank, (int64_t)0);
                 const int64_t e = min((int64_t)pos + a.ref_len + aa.flank, a.glen);

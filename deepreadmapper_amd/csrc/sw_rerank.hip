@@ -28,12 +28,6 @@ namespace {
 constexpr int kPadRow = 256; // profile row index for "matches nothing"
 constexpr uint32_t kNoWindow = 0xFFFFFFFFu; // dynamic lookup: an id whose window lies outside the genome
 
-// comp_table of the reference (src/utils/parse_inputs.cpp:5-14): A<->T, C<->G, N->N, anything else 0
-__device__ __forceinline__ int comp_byte(int c)
-{
-    return c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'N' ? 'N' : 0;
-}
-
 // Bytes of one candidate window: the static table row, or (dynamic lookup, find_sequence
 // src/utils/post_processor.cpp:47-64) genome[w / 2 ..+ ref_len), reverse-complemented for odd w;
 // a window past the genome end is the empty string (every row reads as the pad byte -1).

@@ -170,3 +170,101 @@ def test_pipeline_rejects_ragged_reference(tmp_path):
     q.write_text("A" * 150 + "\n")
     r = subprocess.run([exe, str(prefix), str(q), str(ref)], capture_output=True, text=True)
     assert r.returncode == 1 and "reference sequence 1 has 149 bytes" in r.stderr
+
+
+# bin/pipeline's option checks, all of which run before the index or a device is touched: the environment on top of
+# DRM_SAM_CIGAR=1 (None = unset), the argv positions replaced in `pipeline idx m1.fastq g.fna 128 4 4 out 1 1`, and the
+# text after "Error: " that the binary printed before the options moved into one record (tools/pipeline.cpp)
+_MATES = {"DRM_MATES": "m2.fastq"}
+_RESCUE = {**_MATES, "DRM_PAIR_RESCUE": "1"}
+_MAPQ = {"DRM_SAM_MAPQ": "1"}
+_SCORING_RANGES = ("DRM_SAM_SCORING must be match,mismatch,open,extend with match 1..31, mismatch 1..63, open 0..63, "
+                   "extend 1..63: ")
+_NEEDS_STREAM = "DRM_MATES needs use_dynamic=1 and use_streaming=1: pairs are written to the streamed SAM"
+_MATES_ONE_DEVICE = "DRM_MATES runs on one device (DRM_DEVICE), not on DRM_DEVICES"
+_BAD_OPTIONS = [
+    ("scoring_three", {"DRM_SAM_SCORING": "1,4,6"}, {}, _SCORING_RANGES + '"1,4,6"'),
+    ("scoring_token", {"DRM_SAM_SCORING": "1,4,x,1"}, {},
+     'DRM_SAM_SCORING must be match,mismatch,open,extend (four non-negative integers): "1,4,x,1"'),
+    ("scoring_range", {"DRM_SAM_SCORING": "0,4,6,1"}, {}, _SCORING_RANGES + '"0,4,6,1"'),
+    ("flank_negative", {"DRM_SAM_FLANK": "-1"}, {}, 'DRM_SAM_FLANK must be a non-negative integer: "-1"'),
+    ("flank_wide", {"DRM_SAM_FLANK": "54"}, {}, "DRM_SAM_FLANK 54: ref_len 150 + 2 * flank > 256"),
+    ("tlen_one", {**_MATES, "DRM_PAIR_TLEN": "100"}, {},
+     'DRM_PAIR_TLEN must be min,max (two non-negative integers): "100"'),
+    ("tlen_order", {**_MATES, "DRM_PAIR_TLEN": "500,100"}, {},
+     'DRM_PAIR_TLEN must be min,max with 0 <= min <= max <= 2^30: "500,100"'),
+    ("tlen_token", {**_MATES, "DRM_PAIR_TLEN": "0,1e3"}, {},
+     'DRM_PAIR_TLEN must be min,max (two non-negative integers): "0,1e3"'),
+    ("penalty_negative", {**_MATES, "DRM_PAIR_PENALTY": "-1"}, {},
+     'DRM_PAIR_PENALTY must be an integer in [0, 2^20]: "-1"'),
+    ("pairs_not_streaming", _MATES, {9: "0"}, _NEEDS_STREAM),
+    ("pairs_not_dynamic", _MATES, {8: "0"}, _NEEDS_STREAM),
+    ("pairs_no_cigar", {**_MATES, "DRM_SAM_CIGAR": None}, {},
+     "DRM_MATES needs DRM_SAM_CIGAR=1: the pair fields come from real alignments"),
+    ("mates_missing", {"DRM_MATES": "missing.fastq"}, {}, "Could not open file: missing.fastq"),
+    ("mates_empty", {"DRM_MATES": ""}, {}, "DRM_MATES is empty: it names the file of second mates"),
+    ("mates_short", {"DRM_MATES": "m2short.fastq"}, {},
+     "DRM_MATES: m1.fastq has 2 records and m2short.fastq has 1: record 1 has no mate"),
+    ("mates_renamed", {"DRM_MATES": "m2renamed.fastq"}, {},
+     'DRM_MATES: record 1 is named "r1" in m1.fastq and "x1" in m2renamed.fastq'),
+    ("pairs_two_devices", {**_MATES, "DRM_DEVICES": "0,0"}, {}, _MATES_ONE_DEVICE),
+    ("rescue_min_negative", {**_RESCUE, "DRM_PAIR_RESCUE_MIN": "-1"}, {},
+     'DRM_PAIR_RESCUE_MIN must be an integer in [0, 2^20]: "-1"'),
+    ("rescue_min_token", {**_RESCUE, "DRM_PAIR_RESCUE_MIN": "4x"}, {},
+     'DRM_PAIR_RESCUE_MIN must be an integer in [0, 2^20]: "4x"'),
+    ("rescue_min_empty", {**_RESCUE, "DRM_PAIR_RESCUE_MIN": ""}, {},
+     'DRM_PAIR_RESCUE_MIN must be an integer in [0, 2^20]: ""'),
+    ("rescue_min_large", {**_RESCUE, "DRM_PAIR_RESCUE_MIN": "1048577"}, {},
+     'DRM_PAIR_RESCUE_MIN must be an integer in [0, 2^20]: "1048577"'),
+    ("rescue_window", {**_RESCUE, "DRM_PAIR_TLEN": "0,5000"}, {},
+     "template lengths [0, 5000] at ref_len 150 give a rescue region of 5000 > 2048 rows"),
+    ("mapq_min_negative", {**_MAPQ, "DRM_MAPQ_MIN": "-1"}, {}, 'DRM_MAPQ_MIN must be an integer in [0, 2^20]: "-1"'),
+    ("mapq_min_negative_pairs", {**_MAPQ, **_MATES, "DRM_MAPQ_MIN": "-1"}, {},
+     'DRM_MAPQ_MIN must be an integer in [0, 2^20]: "-1"'),
+    ("mapq_min_token", {**_MAPQ, "DRM_MAPQ_MIN": "4x"}, {}, 'DRM_MAPQ_MIN must be an integer in [0, 2^20]: "4x"'),
+    ("mapq_min_empty", {**_MAPQ, "DRM_MAPQ_MIN": ""}, {}, 'DRM_MAPQ_MIN must be an integer in [0, 2^20]: ""'),
+    ("mapq_min_large", {**_MAPQ, "DRM_MAPQ_MIN": "1048577"}, {},
+     'DRM_MAPQ_MIN must be an integer in [0, 2^20]: "1048577"'),
+    ("mapq_span_zero", {**_MAPQ, "DRM_MAPQ_SPAN": "0"}, {}, 'DRM_MAPQ_SPAN must be an integer in [1, 2^20]: "0"'),
+    ("mapq_span_zero_pairs", {**_MAPQ, **_MATES, "DRM_MAPQ_SPAN": "0"}, {},
+     'DRM_MAPQ_SPAN must be an integer in [1, 2^20]: "0"'),
+    ("mapq_span_token", {**_MAPQ, "DRM_MAPQ_SPAN": "1e2"}, {}, 'DRM_MAPQ_SPAN must be an integer in [1, 2^20]: "1e2"'),
+    ("mapq_span_large", {**_MAPQ, "DRM_MAPQ_SPAN": "1048577"}, {},
+     'DRM_MAPQ_SPAN must be an integer in [1, 2^20]: "1048577"'),
+    ("mapq_two_devices", {**_MAPQ, "DRM_DEVICES": "0,0"}, {},
+     "DRM_SAM_MAPQ runs on one device (DRM_DEVICE), not on DRM_DEVICES"),
+    ("mapq_two_devices_pairs", {**_MAPQ, **_MATES, "DRM_DEVICES": "0,0"}, {}, _MATES_ONE_DEVICE),
+    ("mapq_l2_rows", {**_MAPQ, "DRM_SAM_L2_ROWS": "1"}, {},
+     "DRM_SAM_MAPQ does not go with DRM_SAM_L2_ROWS=1: those rows carry distances, not scores"),
+]
+
+
+@pytest.fixture(scope="module")
+def option_dir(tmp_path_factory):
+    """A prefix directory with nothing but config.txt, and four-base FASTQ files: enough for every option check."""
+    d = tmp_path_factory.mktemp("options")
+    (d / "idx").mkdir()
+    (d / "idx" / "config.txt").write_text("ref_len: 150\nstride: 1\n")
+
+    def fastq(names):
+        return "".join(f"@{n}\n{s}\n+\nIIII\n" for n, s in zip(names, ("ACGT", "TTGA")))
+    (d / "m1.fastq").write_text(fastq(("r0", "r1")))
+    (d / "m2.fastq").write_text(fastq(("r0", "r1")))
+    (d / "m2short.fastq").write_text(fastq(("r0",)))
+    (d / "m2renamed.fastq").write_text(fastq(("r0", "x1")))
+    return d
+
+
+@pytest.mark.parametrize("env,argv,message", [c[1:] for c in _BAD_OPTIONS], ids=[c[0] for c in _BAD_OPTIONS])
+def test_pipeline_rejects_bad_options(option_dir, env, argv, message):
+    """Every fault in argv or a DRM_* variable ends the run with exit status 1 and the same text as before, ahead of
+    the index load (which the directory could not serve)."""
+    args = [os.path.join(ROOT, "bin", "pipeline"), "idx", "m1.fastq", "g.fna", "128", "4", "4", "out", "1", "1"]
+    for i, v in argv.items():
+        args[i] = v
+    e = {k: v for k, v in os.environ.items() if not k.startswith("DRM_")}
+    e.update({k: v for k, v in {"DRM_SAM_CIGAR": "1", **env}.items() if v is not None})
+    r = subprocess.run(args, cwd=option_dir, env=e, capture_output=True, text=True)
+    assert r.returncode == 1
+    assert r.stderr == "Error: " + message + "\n"
+    assert "Index loaded" not in r.stdout
