@@ -24,6 +24,9 @@
 // applied to the 64 nearest candidates (faiss scans all efC); reverse links keep the closest entries
 // instead of re-running the heuristic on the target's list. The graph is therefore not faiss's graph;
 // the file format, levels, entry point and PQ are.
+// The build is a pure function of its inputs (every comparison is on (distance, id), a batch member reads only
+// earlier batches' lists, a list's final set does not depend on the order the CASes land in): tests/builder_ref.py
+// restates steps 2 to 5 in plain Python and tests/test_gpu_builder_exact.py holds the file equal to it link for link.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -534,9 +537,17 @@ void build_hnswpq_gpu(const float *d_x, int64_t n, int d, int M_pq, int nbits, i
     // 4. batched insertion
     int cus = 0;
     DRM_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    const int slots = cus * 16;
+    // test knobs, able only to lower a default: DRM_BUILD_SLOTS the resident waves (each then takes many items on
+    // its one bitmap slot), DRM_BUILD_CLEAR_CAP the clear list (past it a level ends in the full-bitmap clear),
+    // DRM_BUILD_HOP_BOUND and DRM_BUILD_ITEM_BOUND the loop bounds below
+    auto env_bound = [](const char *k, int64_t dflt) {
+        const char *e = std::getenv(k);
+        const int64_t v = e ? std::atoll(e) : 0;
+        return v > 0 ? std::min(v, dflt) : dflt;
+    };
+    const int slots = (int)env_bound("DRM_BUILD_SLOTS", (int64_t)cus * 16);
     const int64_t vis_words = (n + 31) / 32;
-    const int clear_cap = 16384;
+    const int clear_cap = (int)env_bound("DRM_BUILD_CLEAR_CAP", 16384);
     DevArr<uint32_t> dvis((size_t)slots * (size_t)vis_words);
     DRM_HIP_CHECK(hipMemset(dvis.p, 0, sizeof(uint32_t) * (size_t)slots * (size_t)vis_words));
     DevArr<int32_t> dclr((size_t)slots * clear_cap);
@@ -564,11 +575,6 @@ void build_hnswpq_gpu(const float *d_x, int64_t n, int d, int M_pq, int nbits, i
     a.clear_cap = clear_cap;
     a.counter = dcounter.p;
     a.errors = dcounter.p + 1;
-    auto env_bound = [](const char *k, int64_t dflt) {
-        const char *e = std::getenv(k);
-        const int64_t v = e ? std::atoll(e) : 0;
-        return v > 0 ? std::min(v, dflt) : dflt;
-    };
     a.hop_bound = env_bound("DRM_BUILD_HOP_BOUND", n);
     DRM_HIP_CHECK(hipMemset(dcounter.p, 0, 2 * sizeof(uint32_t)));
     const size_t lds = sizeof(float) * 8 * 256;

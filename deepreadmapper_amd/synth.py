@@ -184,6 +184,21 @@ def build_index_gpu_from_rows(rows, path, M_pq=8, nbits=8, M_hnsw=16, efc=200, s
         log(f"[synth] GPU-built IndexHNSWPQ over {n} vectors in {time.time() - t0:.1f}s")
 
 
+def build_index_gpu(x, path, M_pq=8, nbits=8, M_hnsw=16, efc=200, sample_rate=0.5, seed=0, device=0):
+    """GPU build (drm_build_hnswpq_device) over host vectors x [n, 128] f32, uploaded as they are."""
+    from .device import DeviceBuffer, set_device, synchronize
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    set_device(device)
+    d_x = DeviceBuffer.from_host(x)
+    try:
+        check(lib().drm_build_hnswpq_device(d_x.ptr, x.shape[0], x.shape[1], M_pq, nbits, M_hnsw, efc, sample_rate,
+                                            C.c_uint64(seed), device, str(path).encode()))
+        synchronize()
+    finally:
+        d_x.free()
+
+
 def embed_gru(tagged, device=0):
     """GRU embeddings [n, 128] f32 of tagged sequences (rows of a [n, L] u8 array) on the GPU."""
     from .encoder import Encoder

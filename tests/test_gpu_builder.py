@@ -5,7 +5,11 @@
   the host builder's PQ codebook, codes, levels and entry point (same sample, same RNG), and the HIP
   search on it is bit-identical to the oracle on it;
 * its graph is a different (closest-first, batched) HNSW: its recall of the true source window must
-  stay close to the host-built graph's on the same reads."""
+  stay close to the host-built graph's on the same reads.
+
+The exact comparison of that graph lives beside this module: tests/test_gpu_builder_exact.py holds the file equal,
+link for link, to the plain restatement of the build in tests/builder_ref.py (small inputs, every kernel path);
+the tests here cover the file's validity, search parity on it, and the sizes the restatement cannot reach."""
 import os
 import time
 
