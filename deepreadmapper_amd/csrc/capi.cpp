@@ -1475,7 +1475,8 @@ int drm_refs_free(drm_refs *refs)
             return;
         (void)hipSetDevice(refs->dev.device);
         for (void *p : {(void *)refs->dev.windows, (void *)refs->dev.ws_ids, (void *)refs->dev.ws_scores,
-                        (void *)refs->dev.ws_ncand, (void *)refs->dev.genome, (void *)refs->dev.emb})
+                        (void *)refs->dev.ws_ncand, (void *)refs->dev.genome, (void *)refs->dev.emb,
+                        (void *)refs->dev.ws_qoff, refs->dev.ws_scan})
             if (p)
                 (void)hipFree(p);
         delete refs;

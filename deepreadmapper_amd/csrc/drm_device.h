@@ -234,6 +234,10 @@ struct DeviceRefs {
     int32_t *ws_scores = nullptr;
     int32_t *ws_ncand = nullptr;
     size_t ws_elems = 0, ws_nq = 0;
+    // L2 rerank, sparse lists: the expansion stream's prefix sums [nq + 1] and the scan's temporary storage
+    uint64_t *ws_qoff = nullptr;
+    void *ws_scan = nullptr;
+    size_t ws_qoff_n = 0, ws_scan_bytes = 0;
     // dynamic lookup (use_dynamic, post_process_sw_dynamic): the genome string instead of a window
     // table; window id w is genome[w / 2 ..+ ref_len), reverse-complemented when w is odd
     uint8_t *genome = nullptr;

@@ -40,6 +40,7 @@ namespace drm {
 namespace {
 
 constexpr int kBadId = -4;
+constexpr int kReplayMark = -5; // status of a query handed to the tie replay, until the replay has written its rows
 
 // find_sequences' sparse expansion of one label (post_processor.cpp:248-258), size_t arithmetic
 __device__ __forceinline__ void expand(uint64_t id, uint64_t s, uint64_t n, uint64_t &start, uint64_t &cnt)
@@ -54,10 +55,12 @@ __device__ __forceinline__ void expand(uint64_t id, uint64_t s, uint64_t n, uint
     cnt = min(actual + s, n) - start;
 }
 
-// per-query total of the sparse expansion
+// per-query total of the sparse expansion: qcount[0..nq), and qcount[nq] = 0
 __global__ __launch_bounds__(256) void l2_expand_count_kernel(L2Args a, uint64_t *qcount)
 {
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q == a.nq)
+        qcount[q] = 0; // the scan's last input: qcount[nq] becomes the stream length
     if (q >= a.nq)
         return;
     uint64_t tot = 0;
@@ -231,7 +234,8 @@ __device__ void l2_replay_one(const L2Args &a, int cmax, const float *cand_dist,
 // registers (E keys per lane, a bitonic network over 64*E slots, partners across lanes by shuffles). With
 // distinct distances over the first k + 1 sorted positions, the k smallest form a unique ordered set and
 // partial_sort returns exactly it, so the rows are written here. A query with an exact distance tie there is
-// appended to the replay list (replay[0] = count), and the heap replay decides its tie order.
+// marked in its own status word (kReplayMark), a plain store by the block that owns the query, and the heap replay
+// decides its tie order.
 
 __device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m)
 {
@@ -301,7 +305,7 @@ template <int E> __device__ __forceinline__ bool sorted_tie(const uint64_t (&e)[
 
 template <int E>
 __global__ __launch_bounds__(64) void l2_sort_kernel(L2Args a, int cmax, const float *cand_dist,
-                                                     const uint64_t *cand_ids, int32_t *ncand, uint32_t *replay)
+                                                     const uint64_t *cand_ids, int32_t *ncand)
 {
     const int64_t q = blockIdx.x;
     const int lane = threadIdx.x;
@@ -334,8 +338,8 @@ __global__ __launch_bounds__(64) void l2_sort_kernel(L2Args a, int cmax, const f
     bitonic_sort<E>(e, lane);
     const bool tie = sorted_tie<E>(e, lane, a.k, nc);
     if (tie) {
-        if (lane == 0) // replay[0] = count, replay[1 + j] = the j-th handed-over query
-            replay[1 + atomicAdd(replay, 1u)] = (uint32_t)q;
+        if (lane == 0)
+            a.status[q] = kReplayMark;
         return;
     }
     if (lane == 0)
@@ -355,7 +359,7 @@ __global__ __launch_bounds__(64) void l2_sort_kernel(L2Args a, int cmax, const f
 // LDS, and the first wave sorts them (as l2_sort_kernel). The workspace is written only for a query with a tie,
 // for the replay.
 __global__ __launch_bounds__(128) void l2_fused_kernel(L2Args a, int cmax, const uint64_t *qoff, float *cand_dist,
-                                                       uint64_t *cand_ids, uint32_t *replay)
+                                                       uint64_t *cand_ids)
 {
     __shared__ float sq[2][kStageRows * kStagePitch];
     __shared__ uint32_t row_lo[128], row_hi[128];
@@ -431,7 +435,7 @@ __global__ __launch_bounds__(128) void l2_fused_kernel(L2Args a, int cmax, const
             cand_ids[q * cmax + c] = cpos[c];
         }
         if (lane == 0)
-            replay[1 + atomicAdd(replay, 1u)] = (uint32_t)q;
+            a.status[q] = kReplayMark;
         return;
     }
     if (lane == 0)
@@ -446,16 +450,15 @@ __global__ __launch_bounds__(128) void l2_fused_kernel(L2Args a, int cmax, const
     }
 }
 
-// Kernel 3 (tie replay): the queries l2_sort_kernel handed over, one thread each; the grid is sized for the
-// worst case but every thread stops at the device-side count
+// Kernel 3 (tie replay): the queries the sort kernels marked, one thread each; the grid strides over the queries
+// and a thread replays those of its own that carry the mark
 __global__ __launch_bounds__(64) void l2_topk_kernel(L2Args a, int cmax, const float *cand_dist,
-                                                     const uint64_t *cand_ids, const uint32_t *replay)
+                                                     const uint64_t *cand_ids)
 {
     extern __shared__ uint64_t l2_heap[];
-    const uint32_t n_replay = replay[0];
-    for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n_replay; r += gridDim.x * blockDim.x)
-        l2_replay_one(a, cmax, cand_dist, cand_ids, (int64_t)replay[1 + r],
-                      l2_heap + (size_t)threadIdx.x * (size_t)(cmax + 1));
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < a.nq; q += (int64_t)gridDim.x * blockDim.x)
+        if (a.status[q] == kReplayMark)
+            l2_replay_one(a, cmax, cand_dist, cand_ids, q, l2_heap + (size_t)threadIdx.x * (size_t)(cmax + 1));
 }
 
 __global__ void l2_fill_status_kernel(int32_t *ncand, int64_t nq)
@@ -536,24 +539,37 @@ void launch_l2_rerank(DeviceRefs &refs, L2Args a, hipStream_t stream)
         hipLaunchKernelGGL(l2_fill_status_kernel, dim3((unsigned)((a.nq + 255) / 256)), dim3(256), 0, stream,
                            refs.ws_ncand, a.nq);
     uint64_t *qoff = nullptr;
-    void *scan_tmp = nullptr;
     if (a.stride > 1) {
-        // per-query expansion totals -> exclusive prefix qoff[0..nq], qoff[nq] = the stream length
-        DRM_HIP_CHECK(hipMallocAsync((void **)&qoff, sizeof(uint64_t) * (size_t)(a.nq + 1), stream));
-        DRM_HIP_CHECK(hipMemsetAsync(qoff, 0, sizeof(uint64_t) * (size_t)(a.nq + 1), stream));
-        hipLaunchKernelGGL(l2_expand_count_kernel, dim3((unsigned)((a.nq + 255) / 256)), dim3(256), 0, stream, a,
-                           qoff);
+        // per-query expansion totals -> exclusive prefix qoff[0..nq], qoff[nq] = the stream length. Both buffers belong
+        // to the handle's workspace (hipMalloc), like everything else one kernel here writes for the next
+        const size_t nqo = (size_t)a.nq + 1;
+        if (nqo > refs.ws_qoff_n) {
+            if (refs.ws_qoff)
+                DRM_HIP_CHECK(hipFree(refs.ws_qoff));
+            refs.ws_qoff = nullptr;
+            refs.ws_qoff_n = 0;
+            DRM_HIP_CHECK(hipMalloc(&refs.ws_qoff, sizeof(uint64_t) * nqo));
+            refs.ws_qoff_n = nqo;
+        }
+        qoff = refs.ws_qoff;
         size_t tmp_bytes = 0;
-        DRM_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, qoff, qoff, (int)(a.nq + 1), stream));
-        DRM_HIP_CHECK(hipMallocAsync(&scan_tmp, std::max<size_t>(tmp_bytes, 16), stream));
-        DRM_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(scan_tmp, tmp_bytes, qoff, qoff, (int)(a.nq + 1), stream));
+        DRM_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, qoff, qoff, (int)nqo, stream));
+        tmp_bytes = std::max<size_t>(tmp_bytes, 16);
+        if (tmp_bytes > refs.ws_scan_bytes) {
+            if (refs.ws_scan)
+                DRM_HIP_CHECK(hipFree(refs.ws_scan));
+            refs.ws_scan = nullptr;
+            refs.ws_scan_bytes = 0;
+            DRM_HIP_CHECK(hipMalloc(&refs.ws_scan, tmp_bytes));
+            refs.ws_scan_bytes = tmp_bytes;
+        }
+        hipLaunchKernelGGL(l2_expand_count_kernel, dim3((unsigned)((nqo + 255) / 256)), dim3(256), 0, stream, a,
+                           qoff); // nq + 1 threads: every element of qoff is written
+        DRM_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(refs.ws_scan, tmp_bytes, qoff, qoff, (int)nqo, stream));
     }
-    uint32_t *replay = nullptr; // [0] = count, then the handed-over queries
-    DRM_HIP_CHECK(hipMallocAsync((void **)&replay, sizeof(uint32_t) * (size_t)(a.nq + 1), stream));
-    DRM_HIP_CHECK(hipMemsetAsync(replay, 0, sizeof(uint32_t), stream));
     if (nc <= 128) {
         hipLaunchKernelGGL(l2_fused_kernel, dim3((unsigned)a.nq), dim3(128), 0, stream, a, (int)cmax, qoff, cand_dist,
-                           refs.ws_ids, replay);
+                           refs.ws_ids);
     } else {
         const int chunks = (int)((nc + kStageRows - 1) / kStageRows);
         hipLaunchKernelGGL(l2_dist_staged_kernel, dim3((unsigned)(a.nq * chunks)), dim3(kStageRows), 0, stream, a,
@@ -562,15 +578,15 @@ void launch_l2_rerank(DeviceRefs &refs, L2Args a, hipStream_t stream)
         switch (cmax <= 256 ? 4 : cmax <= 512 ? 8 : 16) {
         case 4:
             hipLaunchKernelGGL(l2_sort_kernel<4>, dim3((unsigned)a.nq), dim3(64), 0, stream, a, (int)cmax, cand_dist,
-                               refs.ws_ids, refs.ws_ncand, replay);
+                               refs.ws_ids, refs.ws_ncand);
             break;
         case 8:
             hipLaunchKernelGGL(l2_sort_kernel<8>, dim3((unsigned)a.nq), dim3(64), 0, stream, a, (int)cmax, cand_dist,
-                               refs.ws_ids, refs.ws_ncand, replay);
+                               refs.ws_ids, refs.ws_ncand);
             break;
         default:
             hipLaunchKernelGGL(l2_sort_kernel<16>, dim3((unsigned)a.nq), dim3(64), 0, stream, a, (int)cmax,
-                               cand_dist, refs.ws_ids, refs.ws_ncand, replay);
+                               cand_dist, refs.ws_ids, refs.ws_ncand);
             break;
         }
     }
@@ -578,15 +594,11 @@ void launch_l2_rerank(DeviceRefs &refs, L2Args a, hipStream_t stream)
     int tpb = 64;
     while (tpb > 1 && (size_t)tpb * (size_t)(cmax + 1) * 8 > 65536)
         tpb >>= 1;
-    const int64_t blocks = std::min<int64_t>((a.nq + tpb - 1) / tpb, 128); // ties are rare: a small grid drains the list
+    // ties are rare: a small grid strides over the marks
+    const int64_t blocks = std::min<int64_t>((a.nq + tpb - 1) / tpb, 128);
     hipLaunchKernelGGL(l2_topk_kernel, dim3((unsigned)blocks), dim3(tpb), (size_t)tpb * (size_t)(cmax + 1) * 8,
-                       stream, a, (int)cmax, cand_dist, refs.ws_ids, replay);
+                       stream, a, (int)cmax, cand_dist, refs.ws_ids);
     DRM_HIP_CHECK(hipGetLastError());
-    DRM_HIP_CHECK(hipFreeAsync(replay, stream));
-    if (qoff) {
-        DRM_HIP_CHECK(hipFreeAsync(scan_tmp, stream));
-        DRM_HIP_CHECK(hipFreeAsync(qoff, stream));
-    }
 }
 
 } // namespace drm
