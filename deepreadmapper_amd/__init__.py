@@ -14,6 +14,8 @@ from .rerank import (WindowTable, calc_sw_score, calc_sw_scores, post_process_sw
 from .pairing import PAIR_RESULT_DTYPE, pair_hits, pair_hits_device, sam_pair_fields  # noqa: F401  (paired-end reads)
 from .pairing import (RESCUE_RESULT_DTYPE, mate_rescue, mate_rescue_device, mate_rescue_region,  # noqa: F401
                       mate_rescue_window, pair_rescue_choose)  # (mate rescue)
+from .pairing import (TLEN_ESTIMATE_FIELDS, TLEN_SAMPLE_DTYPE, tlen_estimate, tlen_scan,  # noqa: F401
+                      tlen_scan_device)  # (the template-length window from the reads)
 from .mapq import (MAPQ_RESULT_DTYPE, PAIR_MAPQ_RESULT_DTYPE, hit_mapq, hit_mapq_device, mapq_params,  # noqa: F401
                    mapq_value, pair_mapq, pair_mapq_device, pair_mapq_rescued)  # (mapping quality)
 

@@ -53,6 +53,7 @@ EXPORTS = [
     "drm_pair_rescue_choose",
     "drm_hit_mapq", "drm_hit_mapq_device", "drm_pair_mapq", "drm_pair_mapq_device", "drm_mapq_value",
     "drm_pair_mapq_rescued",
+    "drm_tlen_scan", "drm_tlen_scan_device", "drm_tlen_estimate",
 ]
 
 
@@ -222,6 +223,9 @@ def lib():
         "drm_pair_mapq_device": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i64, vp, vp]),
         "drm_mapq_value": (C.c_int, [i64, i64, i64, i64, i64, C.POINTER(i32)]),
         "drm_pair_mapq_rescued": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, vp]),
+        "drm_tlen_scan": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i64, vp, vp]),
+        "drm_tlen_scan_device": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i64, vp, vp, vp]),
+        "drm_tlen_estimate": (C.c_int, [vp, i32, i32, vp]),
         "drm_exact_search": (C.c_int, [vp, vp, i64, i32, i32, vp, vp, C.POINTER(C.c_double)]),
         "drm_exact_search_device": (C.c_int, [vp, vp, i64, i32, vp, vp, vp]),
         "drm_exact_search_l2": (C.c_int, [vp, i64, i32, vp, i64, i32, vp, vp, C.POINTER(C.c_double)]),

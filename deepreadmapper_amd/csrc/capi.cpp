@@ -2050,6 +2050,78 @@ int drm_pair_mapq(const drm_pair_params *pp, const drm_mapq_params *mp, const ui
     });
 }
 
+// ---------------------------------------------------------------------- template-length scan (tlen_scan.hip)
+// every check that needs no device, in drm_hit_mapq's order; `hist` is required even for no pairs
+static drm::TlenArgs make_tlen_args(const drm_mapq_params *mp, const drm_tlen_params *tp, const uint64_t *ids1,
+                                    const int32_t *scores1, const int32_t *cnt1, const uint64_t *ids2,
+                                    const int32_t *scores2, const int32_t *cnt2, const int32_t *full1,
+                                    const int32_t *full2, int64_t npairs, int32_t k, int64_t row_step,
+                                    drm_tlen_sample *samples, uint32_t *hist)
+{
+    drm::check_mapq_params(mp);
+    if (!tp)
+        throw Error(DRM_ERR_ARG, "null template-length parameters");
+    if (tp->min_mapq < 0 || tp->min_mapq > 60)
+        throw Error(DRM_ERR_ARG, "min_mapq " + std::to_string(tp->min_mapq) + " outside [0, 60]");
+    if (tp->max_scan < mp->ref_len || tp->max_scan > (1 << 16))
+        throw Error(DRM_ERR_ARG, "max_scan " + std::to_string(tp->max_scan) + " outside [ref_len, 2^16]");
+    if (k < 0 || k > drm::kMaxCands)
+        throw Error(DRM_ERR_UNSUPPORTED, "k = " + std::to_string(k) + " outside [0, 1024], the rerank's candidate cap");
+    if (npairs < 0 || row_step < 1)
+        throw Error(DRM_ERR_ARG, "npairs must be >= 0 and row_step >= 1");
+    if (!hist || (npairs > 0 && (!cnt1 || !cnt2 || !full1 || !full2 || (k > 0 && (!ids1 || !scores1 || !ids2 || !scores2)))))
+        throw Error(DRM_ERR_ARG, "null argument");
+    return drm::TlenArgs{*mp, *tp, ids1, scores1, cnt1, ids2, scores2, cnt2, full1, full2, npairs, k, row_step, samples,
+                         hist};
+}
+
+int drm_tlen_scan_device(const drm_mapq_params *mp, const drm_tlen_params *tp, const uint64_t *d_ids1,
+                         const int32_t *d_scores1, const int32_t *d_cnt1, const uint64_t *d_ids2,
+                         const int32_t *d_scores2, const int32_t *d_cnt2, const int32_t *d_full1,
+                         const int32_t *d_full2, int64_t npairs, int32_t k, int64_t row_step,
+                         drm_tlen_sample *d_samples, uint32_t *d_hist, void *stream)
+{
+    return guarded([&] {
+        const drm::TlenArgs a = make_tlen_args(mp, tp, d_ids1, d_scores1, d_cnt1, d_ids2, d_scores2, d_cnt2, d_full1,
+                                               d_full2, npairs, k, row_step, d_samples, d_hist);
+        drm::launch_tlen_scan(a, (hipStream_t)stream);
+    });
+}
+
+int drm_tlen_scan(const drm_mapq_params *mp, const drm_tlen_params *tp, const uint64_t *ids1, const int32_t *scores1,
+                  const int32_t *cnt1, const uint64_t *ids2, const int32_t *scores2, const int32_t *cnt2,
+                  const int32_t *full1, const int32_t *full2, int64_t npairs, int32_t k, int64_t row_step,
+                  drm_tlen_sample *samples, uint32_t *hist)
+{
+    return guarded([&] {
+        drm::TlenArgs a = make_tlen_args(mp, tp, ids1, scores1, cnt1, ids2, scores2, cnt2, full1, full2, npairs, k,
+                                         row_step, samples, hist);
+        const size_t bins = (size_t)3 * ((size_t)tp->max_scan + 1);
+        if (npairs == 0) {
+            std::fill(hist, hist + bins, 0u);
+            return;
+        }
+        check_list_scores(cnt1, scores1, npairs, row_step, k, "mate 1 of pair ");
+        check_list_scores(cnt2, scores2, npairs, row_step, k, "mate 2 of pair ");
+        const size_t rows = list_rows(npairs, row_step);
+        const HitLists d1(ids1, scores1, cnt1, full1, rows, k), d2(ids2, scores2, cnt2, full2, rows, k);
+        DevBuf<drm_tlen_sample> dout(samples ? (size_t)npairs : 0);
+        DevBuf<uint32_t> dhist(bins);
+        DRM_HIP_CHECK(hipMemset(dhist.p, 0, sizeof(uint32_t) * bins));
+        d1.bind(a.ids1, a.scores1, a.cnt1);
+        d2.bind(a.ids2, a.scores2, a.cnt2);
+        a.full1 = d1.full.p;
+        a.full2 = d2.full.p;
+        a.samples = dout.p;
+        a.hist = dhist.p;
+        drm::launch_tlen_scan(a, nullptr);
+        DRM_HIP_CHECK(hipDeviceSynchronize());
+        if (samples)
+            dout.download(samples);
+        dhist.download(hist);
+    });
+}
+
 // ---------------------------------------------------------------------- mate rescue (mate_rescue.hip)
 static drm::RescueArgs make_rescue_args(const drm_refs *refs, const drm_sw_scoring *sc, const drm_pair_params *p,
                                         const uint64_t *anchors, const int64_t *tq, int64_t ntasks, const uint8_t *q,

@@ -379,6 +379,25 @@ struct PairMapqArgs {
 };
 void launch_pair_mapq(const PairMapqArgs &a, hipStream_t stream);
 
+// Template-length scan (tlen_scan.hip; drm_tlen_scan): one wave per pair, the locus scan of each
+// mate's list from its top hit and, where both are confident, one atomic add into the histogram of the pair's class.
+// Runs on the current device and throws Error(DRM_ERR_UNSUPPORTED) for k outside [0, kMaxCands].
+struct TlenArgs {
+    drm_mapq_params prm;
+    drm_tlen_params tlen;
+    const uint64_t *ids1;
+    const int32_t *scores1, *cnt1;
+    const uint64_t *ids2;
+    const int32_t *scores2, *cnt2;
+    const int32_t *full1, *full2; // indexed like cnt1 / cnt2
+    int64_t npairs;
+    int32_t k;
+    int64_t row_step;
+    drm_tlen_sample *samples; // [npairs] or null
+    uint32_t *hist;           // [3][max_scan + 1], added into
+};
+void launch_tlen_scan(const TlenArgs &a, hipStream_t stream);
+
 // L2 rerank (post_process_l2_static -> batch_reranker, src/utils/post_processor.cpp:1023-1162,
 // src/utils/reranker.cpp:98-195): distances from the window embedding table, libstdc++ partial_sort
 struct L2Args {

@@ -775,6 +775,96 @@ extern "C" int drm_pair_mapq_rescued(const drm_mapq_params *mp, const drm_pair_r
     }
 }
 
+// ----------------------------------------------------------------------- template-length window: the estimator
+// (include/drm_hip.h, drm_tlen_estimate). Integers throughout: n < 2^48 (2^16 bins of 32-bit counts), S1 < 2^64,
+// S2 < 2^80 and x * S2 < 2^127, so the sums are 128-bit.
+using u128 = unsigned __int128;
+using i128 = __int128;
+
+static u128 isqrt128(u128 v) // floor(sqrt(v)), one binary digit at a time
+{
+    u128 r = 0, bit = (u128)1 << 126;
+    while (bit > v)
+        bit >>= 2;
+    for (; bit; bit >>= 2) {
+        if (v >= r + bit) {
+            v -= r + bit;
+            r = (r >> 1) + bit;
+        } else {
+            r >>= 1;
+        }
+    }
+    return r;
+}
+
+static drm_tlen_estimate_t tlen_estimate(const uint32_t *h, int32_t nbins, int32_t min_samples)
+{
+    drm_tlen_estimate_t e{};
+    int64_t n = 0;
+    for (int32_t t = 1; t < nbins; ++t)
+        n += h[t];
+    if (n < min_samples) {
+        e.status = 1;
+        return e;
+    }
+    e.n = n;
+    // the quartiles: a[idx] is the first T whose running count passes idx
+    const int64_t idx[3] = {std::min(n - 1, n / 4), std::min(n - 1, 2 * n / 4), std::min(n - 1, 3 * n / 4)};
+    int32_t q[3] = {0, 0, 0};
+    int64_t cum = 0;
+    for (int32_t t = 1, j = 0; t < nbins && j < 3; ++t) {
+        cum += h[t];
+        while (j < 3 && cum > idx[j])
+            q[j++] = t;
+    }
+    e.p25 = q[0];
+    e.p50 = q[1];
+    e.p75 = q[2];
+    const int32_t iqr = e.p75 - e.p25;
+    e.trim_lo = std::max(1, e.p25 - 2 * iqr);
+    e.trim_hi = std::min(nbins - 1, e.p75 + 2 * iqr);
+    u128 s1 = 0, s2 = 0;
+    int64_t x = 0;
+    for (int32_t t = e.trim_lo; t <= e.trim_hi; ++t) {
+        x += h[t];
+        s1 += (u128)h[t] * (u128)t;
+        s2 += (u128)h[t] * (u128)t * (u128)t;
+    }
+    e.n_trim = x;
+    const u128 ux = (u128)x, r = isqrt128(ux * s2 - s1 * s1);
+    e.mean = (int32_t)((2 * s1 + ux) / (2 * ux));
+    e.sd = (int32_t)((2 * r + ux) / (2 * ux));
+    const i128 lo_num = (i128)s1 - 4 * (i128)r;
+    i128 lo = lo_num / (i128)x;
+    if (lo_num % (i128)x < 0) // floor, not truncation
+        --lo;
+    const i128 hi = (i128)((s1 + 4 * r + ux - 1) / ux);
+    e.low = (int32_t)std::max<i128>(1, std::min<i128>(e.p25 - 3 * iqr, lo));
+    e.high = (int32_t)std::max<i128>(e.p75 + 3 * iqr, hi);
+    return e;
+}
+
+extern "C" int drm_tlen_estimate(const uint32_t *hist_row, int32_t nbins, int32_t min_samples,
+                                 drm_tlen_estimate_t *out)
+{
+    try {
+        if (!hist_row || !out)
+            throw drm::Error(DRM_ERR_ARG, "null argument");
+        if (nbins < 2 || nbins > (1 << 16) + 1)
+            throw drm::Error(DRM_ERR_ARG, "nbins " + std::to_string(nbins) + " outside [2, 2^16 + 1]");
+        if (min_samples < 1)
+            throw drm::Error(DRM_ERR_ARG, "min_samples " + std::to_string(min_samples) + " must be >= 1");
+        *out = tlen_estimate(hist_row, nbins, min_samples);
+        return DRM_OK;
+    } catch (const drm::Error &e) {
+        drm::set_last_error(e.what());
+        return e.code;
+    } catch (const std::exception &e) {
+        drm::set_last_error(e.what());
+        return DRM_ERR_ARG;
+    }
+}
+
 void drm::write_sam_pairs(const std::string &path, bool header, const std::string &ref_name, size_t ref_len,
                           const std::vector<std::string> &query_seqs, const std::vector<std::string> &query_ids,
                           size_t q0, size_t npairs, const uint64_t *ids, const int32_t *counts, const int32_t *proper,

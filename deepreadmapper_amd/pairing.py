@@ -1,7 +1,9 @@
 """Paired-end reads: which hit of mate 1 and which hit of mate 2 belong to one fragment (drm_pair_hits, the HIP kernel
 of csrc/pair_hits.hip), the SAM fields that relate a pair's two lines (drm_sam_pair_fields), and the rescue of a mate
 the search lost: its score-only alignment over the insert window of its mate's hit (drm_mate_rescue, the HIP kernel
-of csrc/mate_rescue.hip) and the decision that follows (drm_pair_rescue_choose). The definitions are in
+of csrc/mate_rescue.hip) and the decision that follows (drm_pair_rescue_choose); and the template-length window the
+three of them take, estimated from the reads: the histogram of the confident pairs' template lengths (drm_tlen_scan,
+the HIP kernel of csrc/tlen_scan.hip) and the window read off it (drm_tlen_estimate). The definitions are in
 include/drm_hip.h."""
 import ctypes as C
 
@@ -172,3 +174,79 @@ def pair_rescue_choose(pair, s1, s2, anchor1, anchor2, rA, rB, ref_len, glen, un
                                        int(ref_len), int(glen), int(unpaired_penalty), int(min_score), ptr(out),
                                        C.byref(w)))
     return out[0], int(w.value)
+
+
+# ------------------------------------------------------------------------------------------- template-length window
+# drm_tlen_sample / drm_tlen_estimate_t (include/drm_hip.h)
+TLEN_SAMPLE_DTYPE = np.dtype([(f, np.int32) for f in ("cls", "tlen", "mapq1", "mapq2")])
+TLEN_ESTIMATE_DTYPE = np.dtype([("n", np.int64), ("n_trim", np.int64)] +
+                               [(f, np.int32) for f in ("p25", "p50", "p75", "trim_lo", "trim_hi", "mean", "sd", "low",
+                                                        "high", "status")])
+TLEN_ESTIMATE_FIELDS = TLEN_ESTIMATE_DTYPE.names
+TLEN_MAX_SCAN = 10000    # bin/pipeline's: max(ref_len, 10000)
+TLEN_MIN_MAPQ = 20       # DRM_PAIR_TLEN_MAPQ's default
+TLEN_MIN_SAMPLES = 10    # bwa-mem's
+
+
+def _tlen_params(ref_len, min_mapq, max_scan, locus_span, min_score, sub_band):
+    from .mapq import MAPQ_MIN_DEFAULT, MAPQ_SUB_BAND, mapq_params
+    max_scan = max(int(ref_len), TLEN_MAX_SCAN) if max_scan is None else int(max_scan)
+    mp = mapq_params(ref_len, locus_span, MAPQ_MIN_DEFAULT if min_score is None else min_score,
+                     MAPQ_SUB_BAND if sub_band is None else sub_band)
+    return mp, np.array([int(min_mapq), max_scan], dtype=np.int32), max_scan
+
+
+def tlen_scan(ids1, scores1, cnt1, ids2, scores2, cnt2, full1, full2, ref_len, min_mapq=TLEN_MIN_MAPQ, max_scan=None,
+              row_step=1, locus_span=None, min_score=None, sub_band=None, samples=True):
+    """drm_tlen_scan on host arrays: the lists and full_m as pair_mapq takes them (row_step included); the MAPQ
+    parameters default to mapq_params', max_scan to max(ref_len, 10000). Returns (samples, hist): a structured array
+    (TLEN_SAMPLE_DTYPE), one record per pair (None with samples=False), and the histogram [3, max_scan + 1] u32 of the
+    FR, RF and same-strand template lengths."""
+    i1, i2 = _rows(ids1, np.uint64), _rows(ids2, np.uint64)
+    s1, s2 = _rows(scores1, np.int32), _rows(scores2, np.int32)
+    c1, c2 = np.ascontiguousarray(cnt1, dtype=np.int32), np.ascontiguousarray(cnt2, dtype=np.int32)
+    f1, f2 = np.ascontiguousarray(full1, dtype=np.int32), np.ascontiguousarray(full2, dtype=np.int32)
+    k, row_step = int(i1.shape[1]), int(row_step)
+    if row_step < 1:
+        raise ValueError("row_step must be >= 1")
+    if not (i1.ndim == 2 and i1.shape == s1.shape and i2.shape == s2.shape and i2.shape[1] == k and
+            len(c1) == len(i1) and len(c2) == len(i2) and f1.shape == c1.shape and f2.shape == c2.shape):
+        raise ValueError("ids, scores [rows, k] and counts, full [rows] of a mate must agree, and k of the two mates")
+    npairs = (len(c1) + row_step - 1) // row_step
+    if npairs and (npairs - 1) * row_step + 1 > len(c2):
+        raise ValueError("mate 2 has fewer rows than the pairs of mate 1 need")
+    mp, tp, max_scan = _tlen_params(ref_len, min_mapq, max_scan, locus_span, min_score, sub_band)
+    out = np.zeros(npairs, dtype=TLEN_SAMPLE_DTYPE) if samples else None
+    hist = np.zeros((3, max(max_scan, 0) + 1), dtype=np.uint32)
+    check(lib().drm_tlen_scan(ptr(mp), ptr(tp), ptr(i1) if i1.size else None, ptr(s1) if s1.size else None, ptr(c1),
+                              ptr(i2) if i2.size else None, ptr(s2) if s2.size else None, ptr(c2), ptr(f1), ptr(f2),
+                              npairs, k, row_step, ptr(out), ptr(hist)))
+    return out, hist
+
+
+def tlen_scan_device(d_ids1, d_scores1, d_cnt1, d_ids2, d_scores2, d_cnt2, d_full1, d_full2, npairs, k, ref_len, d_hist,
+                     min_mapq=TLEN_MIN_MAPQ, max_scan=None, row_step=1, locus_span=None, min_score=None, sub_band=None,
+                     d_samples=None, stream=None):
+    """drm_tlen_scan_device: the same on device memory, enqueued on `stream`. Each d_* argument is a DeviceBuffer or a
+    raw device address. ADDS into d_hist ([3, max_scan + 1] u32, zeroed by the caller); d_samples (npairs records of
+    TLEN_SAMPLE_DTYPE) may be None. Returns d_hist; synchronise the stream before downloading it."""
+    def addr(b):
+        return None if b is None else C.c_void_p(b.ptr if hasattr(b, "ptr") else int(b))
+    mp, tp, _ = _tlen_params(ref_len, min_mapq, max_scan, locus_span, min_score, sub_band)
+    check(lib().drm_tlen_scan_device(ptr(mp), ptr(tp), addr(d_ids1), addr(d_scores1), addr(d_cnt1), addr(d_ids2),
+                                     addr(d_scores2), addr(d_cnt2), addr(d_full1), addr(d_full2), int(npairs), int(k),
+                                     int(row_step), addr(d_samples), addr(d_hist),
+                                     stream.handle if stream is not None else None))
+    return d_hist
+
+
+def tlen_estimate(hist_row, min_samples=TLEN_MIN_SAMPLES):
+    """drm_tlen_estimate: the template-length window of one histogram row (bin T = the number of samples of template
+    length T), as a dict over TLEN_ESTIMATE_FIELDS; status 1 (every other field 0) below min_samples samples. `low` and
+    `high` are the window to map with. Host only."""
+    h = np.ascontiguousarray(hist_row, dtype=np.uint32)
+    if h.ndim != 1:
+        raise ValueError("one histogram row")
+    out = np.zeros(1, dtype=TLEN_ESTIMATE_DTYPE)
+    check(lib().drm_tlen_estimate(ptr(h) if h.size else None, len(h), int(min_samples), ptr(out)))
+    return {f: int(out[f][0]) for f in TLEN_ESTIMATE_FIELDS}

@@ -618,6 +618,65 @@ int drm_pair_mapq_rescued(const drm_mapq_params *mp, const drm_pair_result *pair
                           const int32_t *full1, const int32_t *full2, int64_t npairs, int64_t row_step,
                           drm_pair_mapq_result *inout);
 
+/* ---------------------------------------------------------------- Template-length window from the reads
+ * drm_pair_hits, drm_mate_rescue and drm_pair_mapq all take the window [min_tlen, max_tlen] a proper pair's template
+ * length must lie in. It is a property of the sequenced library, so it is estimated from the batch being mapped, as
+ * bwa-mem does in mem_pestat: the pairs whose two mates each map uniquely on their own are turned into a histogram of
+ * template lengths (drm_tlen_scan), and the window is read off the histogram (drm_tlen_estimate). The reference has no
+ * paired mode, so this text is the definition.
+ * Scan. Lists, counts, row_step, the indexing of full_m and the hit model are drm_pair_mapq's, word for word; the
+ * argument ranges are drm_hit_mapq's (0 <= k <= 1024, beyond: DRM_ERR_UNSUPPORTED; scores of the counted rows in
+ * [0, 2^20]: the host form checks them, DRM_ERR_ARG, for the device form they are the caller's contract), with
+ * 0 <= min_mapq <= 60 and ref_len <= max_scan <= 2^16 (DRM_ERR_ARG outside). For pair p:
+ *   1. mapq_m = the mapq field of drm_hit_mapq's record of mate m's list with head -1 and self score full_m; 0 when
+ *      that record's status is 1. mapq1 and mapq2 are always reported.
+ *   2. Mate m is confident iff mapq_m >= min_mapq and its record's status is 0. Not both confident: cls = 0, tlen = 0.
+ *   3. Otherwise w1, w2 = the ids of the two records' `best` rows, and in 64-bit arithmetic (any u64 id is safe):
+ *        rev(w1) == rev(w2):  cls = 3 (same strand), T = |pos(w1) - pos(w2)| + ref_len;
+ *        otherwise, with f the forward hit, r the reverse hit and d = pos(r) - pos(f):
+ *          d >= 0: cls = 1 (FR), T = d + ref_len -- drm_pair_hits' T;
+ *          d < 0:  cls = 2 (RF), T = -d + ref_len;
+ *        T > max_scan: cls = 4 (far), tlen = 0; otherwise tlen = T.
+ * Histogram: hist[(cls - 1) * (max_scan + 1) + T] += 1 for cls 1 to 3, three rows of max_scan + 1 bins. The host form
+ * zeroes hist first; the device form ADDS into d_hist, which the caller zeroes and may accumulate over several calls.
+ * The counts are integers: the result does not depend on the order in which the pairs finish. samples / d_samples
+ * [npairs] may be NULL. */
+typedef struct {
+    int32_t min_mapq, max_scan;
+} drm_tlen_params;
+typedef struct {
+    int32_t cls, tlen, mapq1, mapq2;
+} drm_tlen_sample;
+int drm_tlen_scan(const drm_mapq_params *mp, const drm_tlen_params *tp, const uint64_t *ids1, const int32_t *scores1,
+                  const int32_t *cnt1, const uint64_t *ids2, const int32_t *scores2, const int32_t *cnt2,
+                  const int32_t *full1, const int32_t *full2, int64_t npairs, int32_t k, int64_t row_step,
+                  drm_tlen_sample *samples, uint32_t *hist);
+/* Device-buffer form, enqueued on `stream`. Stateless: no handle, the current device. It consumes
+ * drm_post_process_sw_{static,dynamic}_device's d_top_ids, d_top_scores and d_status unchanged. */
+int drm_tlen_scan_device(const drm_mapq_params *mp, const drm_tlen_params *tp, const uint64_t *d_ids1,
+                         const int32_t *d_scores1, const int32_t *d_cnt1, const uint64_t *d_ids2,
+                         const int32_t *d_scores2, const int32_t *d_cnt2, const int32_t *d_full1,
+                         const int32_t *d_full2, int64_t npairs, int32_t k, int64_t row_step,
+                         drm_tlen_sample *d_samples, uint32_t *d_hist, void *stream);
+/* Host only, no device, integers throughout: the window of one histogram row, hist_row[nbins] with bin T the number
+ * of samples of template length T. The steps are bwa-mem's mem_pestat (outliers beyond 2 IQR, mapping bound 3 IQR,
+ * 4 standard deviations) restated on a histogram:
+ *   1. n = the sum of hist_row[T] over T in [1, nbins). n < min_samples: status 1, every other field 0. Otherwise
+ *      status 0.
+ *   2. With a[0..n) the samples in ascending order, p25, p50, p75 = a[min(n - 1, floor(q * n / 4))], q = 1, 2, 3.
+ *   3. iqr = p75 - p25; trim_lo = max(1, p25 - 2 * iqr); trim_hi = min(nbins - 1, p75 + 2 * iqr).
+ *   4. Over the samples in [trim_lo, trim_hi]: x = n_trim their number (>= 1), S1 = sum T, S2 = sum T^2, both exact
+ *      (128 bits); V = x * S2 - S1^2 (>= 0); R = floor(sqrt(V)), an integer square root.
+ *   5. mean = floor((2 * S1 + x) / (2 * x)); sd = floor((2 * R + x) / (2 * x)): both rounded half up.
+ *   6. low = max(1, min(p25 - 3 * iqr, floor((S1 - 4 * R) / x))), the division flooring toward minus infinity.
+ *   7. high = max(p75 + 3 * iqr, ceil((S1 + 4 * R) / x)).
+ * DRM_ERR_ARG: a null pointer, nbins outside [2, 2^16 + 1], min_samples < 1. */
+typedef struct {
+    int64_t n, n_trim;
+    int32_t p25, p50, p75, trim_lo, trim_hi, mean, sd, low, high, status;
+} drm_tlen_estimate_t;
+int drm_tlen_estimate(const uint32_t *hist_row, int32_t nbins, int32_t min_samples, drm_tlen_estimate_t *out);
+
 /* ---------------------------------------------------------------- L2 rerank (the reference's live path)
  * post_process_l2_static (src/utils/post_processor.cpp:1023-1162, called at src/main.cpp:330) ->
  * find_sequences (static) -> Vectorizer::vectorize of the candidate windows -> batch_reranker(k = k_clusters)

@@ -21,6 +21,9 @@
 // PNEXT and TLEN (drm_sam_pair_fields). DRM_PAIR_RESCUE=1 beside it rescues the mates the search lost: a pair without a
 // proper combination has each read aligned against the insert window of its mate's hit (drm_mate_rescue), and a
 // rescued mate that scores at least DRM_PAIR_RESCUE_MIN=n replaces the unpaired choice (drm_pair_rescue_choose).
+// DRM_PAIR_TLEN=auto estimates the window from the first DRM_PAIR_TLEN_SAMPLE=n pairs before the block loop: the
+// template lengths of the pairs whose mates both reach MAPQ DRM_PAIR_TLEN_MAPQ=n alone (drm_tlen_scan_device), then
+// bwa-mem's quartile rule on their histogram (drm_tlen_estimate); the run goes on as with DRM_PAIR_TLEN=<min>,<max>.
 // DRM_SAM_MAPQ=1 (with use_dynamic=1 use_streaming=1 DRM_SAM_CIGAR=1, one device) replaces the constant MAPQ 60 by the
 // locus scan of each read's rerank rows (drm_hit_mapq; for pairs drm_pair_mapq and drm_pair_mapq_rescued), with
 // DRM_MAPQ_MIN=n and DRM_MAPQ_SPAN=n; the SW rerank then runs whatever the stride, as with DRM_MATES.
@@ -242,13 +245,35 @@ static bool affine_mode_from_env(size_t ref_len, AffineMode &mode)
 // drm_pair_hits' ranges before any work. DRM_PAIR_RESCUE=1 turns the mate rescue on; only then is DRM_PAIR_RESCUE_MIN=n
 // (0 to 2^20, the score a rescued mate needs) read, as strictly, and the template-length window checked against
 // drm_mate_rescue's 2,048-row cap.
+// DRM_PAIR_TLEN=auto instead of min,max: the window is estimated from the first DRM_PAIR_TLEN_SAMPLE=n pairs (default
+// 65,536, 1 to 2^24) before the block loop, from the pairs whose mates both reach MAPQ DRM_PAIR_TLEN_MAPQ=n (default
+// 20, 0 to 60) on their own (Pipeline::estimate_tlen); both variables are read only then, as strictly. The rescue's cap
+// is then checked on the estimated window.
 constexpr int32_t kRescueMinDefault = 49; // the largest chance score measured, 39, plus 10
+constexpr int32_t kRescueMaxRows = 2048;  // drm_mate_rescue's cap on dhi - dlo + ref_len
+constexpr int32_t kTlenMinSamples = 10;   // bwa-mem's
 struct PairMode {
     std::string mates;
     drm_pair_params prm;
     bool rescue = false;
     int32_t rescue_min = kRescueMinDefault;
+    bool tlen_auto = false;
+    size_t tlen_sample = (size_t)1 << 16;
+    int32_t tlen_mapq = 20;
 };
+
+// `name`, when set, into v: an integer in [lo, hi]
+static void env_range(const char *name, long lo, long hi, long &v)
+{
+    const char *e = std::getenv(name);
+    if (!e)
+        return;
+    long x = 0;
+    if (!parse_int(e, x) || x < lo || x > hi)
+        throw drm::Error(DRM_ERR_ARG, std::string(name) + " must be an integer in [" + std::to_string(lo) + ", " +
+                                          std::to_string(hi) + "]: " + quoted(e));
+    v = x;
+}
 
 static bool pair_mode_from_env(size_t ref_len, PairMode &mode)
 {
@@ -261,7 +286,15 @@ static bool pair_mode_from_env(size_t ref_len, PairMode &mode)
         throw drm::Error(DRM_ERR_UNSUPPORTED, "DRM_MATES: ref_len " + std::to_string(ref_len) + " outside [1, 2^20]");
     mode.mates = mates;
     mode.prm = drm_pair_params{(int32_t)ref_len, 0, 1000, 17};
-    if (const char *tl = std::getenv("DRM_PAIR_TLEN")) {
+    const char *tl = std::getenv("DRM_PAIR_TLEN");
+    if (tl && std::string(tl) == "auto") {
+        long n = (long)mode.tlen_sample, q = mode.tlen_mapq;
+        env_range("DRM_PAIR_TLEN_SAMPLE", 1, 1L << 24, n);
+        env_range("DRM_PAIR_TLEN_MAPQ", 0, 60, q);
+        mode.tlen_auto = true;
+        mode.tlen_sample = (size_t)n;
+        mode.tlen_mapq = (int32_t)q;
+    } else if (tl) {
         long v[2] = {};
         if (parse_int_list(tl, 2, v) != 2)
             throw drm::Error(DRM_ERR_ARG, "DRM_PAIR_TLEN must be min,max (two non-negative integers): " + quoted(tl));
@@ -275,7 +308,8 @@ static bool pair_mode_from_env(size_t ref_len, PairMode &mode)
     if (mode.rescue) {
         env_int("DRM_PAIR_RESCUE_MIN", 0, mode.rescue_min);
         int64_t dlo = 0, dhi = 0;
-        drm::check_rescue_params(&mode.prm, dlo, dhi); // DRM_PAIR_TLEN wider than the rescue's 2,048 rows
+        if (!mode.tlen_auto)
+            drm::check_rescue_params(&mode.prm, dlo, dhi); // DRM_PAIR_TLEN wider than the rescue's 2,048 rows
     }
     return true;
 }
@@ -284,16 +318,23 @@ static bool pair_mode_from_env(size_t ref_len, PairMode &mode)
 // each read's rerank rows (drm_hit_mapq, drm_pair_mapq) instead of the constant 60. DRM_MAPQ_MIN=n (default 39, the
 // largest chance score DESIGN.md sec. 4.11 recorded for 150-base reads) and DRM_MAPQ_SPAN=n (default ref_len) are read
 // only then, as strictly as DRM_SAM_SCORING; sub_band is 2, one substitution under the rerank's scoring {1, 1, 0, 1}.
+// DRM_PAIR_TLEN=auto scans with the same parameters, whether or not DRM_SAM_MAPQ is on.
 constexpr int32_t kMapqMinDefault = 39;
+static drm_mapq_params mapq_params_from_env(size_t ref_len)
+{
+    drm_mapq_params prm{(int32_t)ref_len, (int32_t)ref_len, kMapqMinDefault, 2};
+    env_int("DRM_MAPQ_MIN", 0, prm.min_score);
+    env_int("DRM_MAPQ_SPAN", 1, prm.locus_span);
+    return prm;
+}
+
 static bool mapq_mode_from_env(size_t ref_len, bool l2_rows, drm_mapq_params &prm)
 {
     if (!env_flag("DRM_SAM_MAPQ"))
         return false;
     if (ref_len < 1 || ref_len > ((size_t)1 << 20))
         throw drm::Error(DRM_ERR_UNSUPPORTED, "DRM_SAM_MAPQ: ref_len " + std::to_string(ref_len) + " outside [1, 2^20]");
-    prm = drm_mapq_params{(int32_t)ref_len, (int32_t)ref_len, kMapqMinDefault, 2};
-    env_int("DRM_MAPQ_MIN", 0, prm.min_score);
-    env_int("DRM_MAPQ_SPAN", 1, prm.locus_span);
+    prm = mapq_params_from_env(ref_len);
     if (l2_rows)
         throw drm::Error(DRM_ERR_ARG, "DRM_SAM_MAPQ does not go with DRM_SAM_L2_ROWS=1: those rows carry distances, "
                                       "not scores");
@@ -347,6 +388,10 @@ static Options read_options(int argc, char *argv[], size_t ref_len, size_t strid
     o.has_affine = cigar && affine_mode_from_env(ref_len, o.affine_mode);
     o.paired = pair_mode_from_env(ref_len, o.pair);
     o.mapq = use_dynamic && o.use_streaming && cigar && !o.is_npy && mapq_mode_from_env(ref_len, l2_rows, o.mapq_prm);
+    if (!o.paired && std::getenv("DRM_PAIR_TLEN") && std::string(std::getenv("DRM_PAIR_TLEN")) == "auto")
+        throw drm::Error(DRM_ERR_ARG, "DRM_PAIR_TLEN=auto needs DRM_MATES: the window is estimated from read pairs");
+    if (o.paired && o.pair.tlen_auto && !o.mapq)
+        o.mapq_prm = mapq_params_from_env(ref_len);
     if (o.paired) {
         if (!use_dynamic || !o.use_streaming)
             throw drm::Error(DRM_ERR_ARG, "DRM_MATES needs use_dynamic=1 and use_streaming=1: pairs are written to the "
@@ -458,8 +503,12 @@ struct Pipeline {
     Pinned<int64_t> I;
     Pinned<uint64_t> sw_ids;
     drm_search_stats st{};
+    drm_pair_params pair_prm; // o.pair.prm, with DRM_PAIR_TLEN=auto the estimated window from estimate_tlen on
 
-    explicit Pipeline(const Options &opt) : o(opt), k((size_t)opt.k), kc((size_t)opt.k_clusters), device(opt.devices[0]) {}
+    explicit Pipeline(const Options &opt)
+        : o(opt), k((size_t)opt.k), kc((size_t)opt.k_clusters), device(opt.devices[0]), pair_prm(opt.pair.prm)
+    {
+    }
 
     // false: a sequence file without a record
     bool load_queries()
@@ -775,7 +824,7 @@ struct Pipeline {
         if (anchors.empty())
             return;
         const drm_sw_scoring rerank_scoring{1, 1, 0, 1};
-        const drm_pair_params &prm = o.pair.prm;
+        const drm_pair_params &prm = pair_prm;
         std::vector<drm_rescue_result> out(anchors.size());
         check(drm_mate_rescue(art, &rerank_scoring, &prm, anchors.data(), tq.data(), (int64_t)anchors.size(),
                               qbuf.p + lo * qs, ql.p + lo, (int32_t)qs, (int64_t)(2 * np), out.data()));
@@ -802,6 +851,82 @@ struct Pipeline {
         }
     }
 
+    // DRM_PAIR_TLEN=auto, before the block loop: the first min(pairs, DRM_PAIR_TLEN_SAMPLE) pairs are searched and
+    // reranked as the block loop does it, drm_tlen_scan_device turns their rows (drm_search_rerank hands them over in
+    // host memory, so they are uploaded once more) into the histogram of the confident pairs' template lengths, and
+    // drm_tlen_estimate reads the window off its FR row into pair_prm. Fewer than kTlenMinSamples FR pairs: the default
+    // 0,1000 stays. The rows are dropped: the block loop computes them again, so the file is that of the run with
+    // DRM_PAIR_TLEN=<min>,<max> whatever DRM_SAM_BLOCK says.
+    void estimate_tlen()
+    {
+        struct DeviceMem {
+            void *p = nullptr;
+            DeviceMem(const void *host, size_t bytes)
+            {
+                check(drm_malloc(&p, std::max<size_t>(bytes, 1)));
+                if (host && bytes)
+                    check(drm_memcpy_h2d(p, host, bytes));
+            }
+            ~DeviceMem() { drm_free(p); }
+            DeviceMem(const DeviceMem &) = delete;
+            DeviceMem &operator=(const DeviceMem &) = delete;
+        };
+        const size_t np = std::min(nq / 2, o.pair.tlen_sample), m = 2 * np;
+        const int32_t ref_len = (int32_t)o.ref_len;
+        const drm_tlen_params tp{o.pair.tlen_mapq, std::max(ref_len, 10000)};
+        const size_t bins = (size_t)tp.max_scan + 1;
+        std::vector<uint32_t> hist(3 * bins, 0);
+        std::vector<drm_tlen_sample> samples(np);
+        if (np) {
+            drm_search_stats unused{};
+            check(search(0, m, &unused));
+            std::vector<int32_t> full(m);
+            for (size_t r = 0; r < m; ++r)
+                full[r] = untagged_length(qseqs[r]);
+            check(drm_set_device(device));
+            const DeviceMem d_ids(sw_ids.p, sizeof(uint64_t) * m * k), d_sc(sw_scores.p, sizeof(int32_t) * m * k),
+                d_cnt(status.p, sizeof(int32_t) * m), d_full(full.data(), sizeof(int32_t) * m),
+                d_hist(hist.data(), sizeof(uint32_t) * hist.size()), d_samples(nullptr, sizeof(drm_tlen_sample) * np);
+            const uint64_t *ids = static_cast<const uint64_t *>(d_ids.p);
+            const int32_t *sc = static_cast<const int32_t *>(d_sc.p), *cnt = static_cast<const int32_t *>(d_cnt.p),
+                          *fl = static_cast<const int32_t *>(d_full.p);
+            check(drm_tlen_scan_device(&o.mapq_prm, &tp, ids, sc, cnt, ids + k, sc + k, cnt + 1, fl, fl + 1, (int64_t)np,
+                                       o.k, 2, static_cast<drm_tlen_sample *>(d_samples.p),
+                                       static_cast<uint32_t *>(d_hist.p), nullptr));
+            check(drm_device_sync());
+            check(drm_memcpy_d2h(hist.data(), d_hist.p, sizeof(uint32_t) * hist.size()));
+            check(drm_memcpy_d2h(samples.data(), d_samples.p, sizeof(drm_tlen_sample) * np));
+        }
+        drm_tlen_estimate_t e{};
+        check(drm_tlen_estimate(hist.data(), (int32_t)bins, kTlenMinSamples, &e));
+        uint64_t cls[5] = {};
+        for (const drm_tlen_sample &s : samples)
+            ++cls[std::clamp(s.cls, 0, 4)];
+        std::ostringstream classes;
+        classes << "FR/RF/same/far = " << cls[1] << "/" << cls[2] << "/" << cls[3] << "/" << cls[4];
+        if (e.status != 0) {
+            std::cout << "[MAIN] Template length (auto): " << cls[1] << " FR pairs among " << np << " sampled, fewer than "
+                      << kTlenMinSamples << ": falling back to min=" << pair_prm.min_tlen << " max=" << pair_prm.max_tlen
+                      << "; " << classes.str() << std::endl;
+        } else {
+            // drm_mate_rescue scans dhi - dlo + ref_len rows, 2,048 at the most: the widest max_tlen it admits
+            const int32_t widest = std::max(0, e.low - ref_len) + kRescueMaxRows;
+            const bool cut = o.pair.rescue && e.high > widest;
+            pair_prm.min_tlen = e.low;
+            pair_prm.max_tlen = cut ? widest : e.high;
+            std::cout << "[MAIN] Template length (auto): min=" << pair_prm.min_tlen << " max=" << pair_prm.max_tlen
+                      << " mean=" << e.mean << " sd=" << e.sd << " from " << e.n << " of " << np << " pairs; "
+                      << classes.str();
+            if (cut)
+                std::cout << " (max cut from " << e.high << " to the mate rescue's " << kRescueMaxRows << "-row cap)";
+            std::cout << std::endl;
+        }
+        if (o.pair.rescue) {
+            int64_t dlo = 0, dhi = 0;
+            drm::check_rescue_params(&pair_prm, dlo, dhi);
+        }
+    }
+
     // One block of pairs [p0, p0 + mp), searched and reranked as 2 * mp interleaved reads: drm_pair_hits over the
     // block's lists (row_step 2), the alignment of only the chosen row of every read, and the two lines per pair.
     std::function<void()> produce_pairs(size_t p0, size_t mp)
@@ -814,7 +939,7 @@ struct Pipeline {
         auto ba = std::make_shared<BlockAlignments>();
         std::vector<drm_pair_result> res(mp);
         check(drm_set_device(device));
-        check(drm_pair_hits(&o.pair.prm, sw_ids.p + at, sw_scores.p + at, status.p + lo, sw_ids.p + at + k,
+        check(drm_pair_hits(&pair_prm, sw_ids.p + at, sw_scores.p + at, status.p + lo, sw_ids.p + at + k,
                             sw_scores.p + at + k, status.p + lo + 1, (int64_t)mp, o.k, 2, res.data()));
         for (size_t p = 0; p < mp; ++p) {
             const int32_t j[2] = {res[p].j1, res[p].j2};
@@ -832,7 +957,7 @@ struct Pipeline {
         if (o.mapq) {
             for (size_t r = 0; r < m; ++r)
                 full[r] = untagged_length(qseqs[lo + r]);
-            check(drm_pair_mapq(&o.pair.prm, &o.mapq_prm, sw_ids.p + at, sw_scores.p + at, status.p + lo,
+            check(drm_pair_mapq(&pair_prm, &o.mapq_prm, sw_ids.p + at, sw_scores.p + at, status.p + lo,
                                 sw_ids.p + at + k, sw_scores.p + at + k, status.p + lo + 1, full.data(), full.data() + 1,
                                 res.data(), (int64_t)mp, o.k, 2, pm.data()));
             after = res;
@@ -905,6 +1030,8 @@ struct Pipeline {
             return write_sparse_sam();
         if (!o.stream_sam)
             return search(0, nq, &st);
+        if (o.paired && o.pair.tlen_auto)
+            estimate_tlen();
         open_sam(o.paired ? " (paired)" : "");
         if (o.paired) // DRM_SAM_BLOCK counts pairs here; the file does not depend on it
             return stream_blocks(nq / 2, 2, o.block(2), [&](size_t p0, size_t mp) { return produce_pairs(p0, mp); });
