@@ -130,8 +130,8 @@ int64_t search_hop_bound(const DeviceIndex &ix);
 int64_t search_item_bound(const DeviceIndex &ix, int64_t n);
 void launch_hnsw_search(DeviceIndex &ix, const float *d_x, int64_t n, int k, int ef, float *d_D, int64_t *d_I,
                         int32_t *d_ndis, int32_t *d_nhops, int32_t *d_nhops_upper, hipStream_t stream);
-void launch_hnsw_search_lds(DeviceIndex &ix, const float *d_x, int64_t n, int k, int ef, float *d_D, int64_t *d_I,
-                            int32_t *d_ndis, int32_t *d_nhops, int32_t *d_nhops_upper, hipStream_t stream);
+// LDS-heap kernel (hnsw_search_lds.hip): max(efSearch, k) in (512, 4096], or forced; launch_hnsw_search sizes lds_bytes
+void launch_hnsw_pq_lds(const SearchArgs &a, int slots, size_t lds_bytes, bool fast8, hipStream_t stream);
 
 // ---------------------------------------------------------------------- fp32 (hnswlib) index
 // HBM image of an hnswlib HierarchicalNSW<float> (DESIGN.md "fp32 mode").

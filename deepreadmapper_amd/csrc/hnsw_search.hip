@@ -715,68 +715,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void hn
 }
 
 
-} // namespace
+// ---------------------------------------------------------------------------------------------- host side
+// One path from (index, n, k, ef) to a launch: check_search_limits, plan_search (which kernel,
+// how many slots, how much LDS; no HIP call), ensure_visited / ensure_log / ensure_counter (the only places that
+// allocate the per-handle workspace and account for it in device_bytes), make_search_args (the one SearchArgs fill).
+constexpr size_t kLdsPerCu = 160 * 1024;
 
-// Per-slot search workspace (visited bitmaps, clear lists, queue counters, the lean kernel's push log)
-// for a full-occupancy grid, allocated once at index load so that no search pays for it (at C5 a bitmap
-// workspace is 32 GB). Searches that need more (other LUT sizes, larger logs) still grow it. The lean kernel
-// keeps no visited table: with inline rows the bitmap waits for a search that needs it (another kernel, or
-// exact statistics).
-void reserve_search_scratch(DeviceIndex &ix)
+size_t lut_bytes(const DeviceIndex &ix) { return sizeof(float) * (size_t)ix.pq_M * ix.ksub; }
+// resident waves per CU of the register-heap and lean kernels, whose only LDS is the LUT
+int lut_waves_per_cu(const DeviceIndex &ix) { return std::max(1, std::min(ix.waves_per_cu, (int)(kLdsPerCu / lut_bytes(ix)))); }
+// the lean kernel's push log per slot: a compacted log holds <= k <= ef entries; then up to 64 staged evictions, or
+// the ef heap entries at the end
+int search_log_cap(const DeviceIndex &ix, int efc) { return std::max(ix.log_cap_req, efc + std::max(efc, 64)); }
+
+void check_search_limits(const DeviceIndex &ix, int k, int efc)
 {
-    int cus = 0;
-    DRM_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ix.device));
-    const size_t lds = sizeof(float) * (size_t)ix.pq_M * ix.ksub;
-    if (lds == 0 || lds > 160 * 1024)
-        return;
-    const int per_cu = std::max(1, std::min(ix.waves_per_cu, (int)((160 * 1024) / lds)));
-    const int slots = cus * per_cu;
-    if (!ix.rows) {
-        ix.vis_words = std::max<int64_t>((ix.ntotal + 31) / 32, 1);
-        ix.clear_cap = 16384;
-        DRM_HIP_CHECK(malloc_big((void **)&ix.visited, sizeof(uint32_t) * (size_t)slots * (size_t)ix.vis_words, kBigVisited));
-        DRM_HIP_CHECK(hipMemset(ix.visited, 0, sizeof(uint32_t) * (size_t)slots * (size_t)ix.vis_words));
-        DRM_HIP_CHECK(hipMalloc(&ix.clear_list, sizeof(int32_t) * (size_t)slots * (size_t)ix.clear_cap));
-        ix.n_slots = slots;
-        ix.device_bytes += (int64_t)sizeof(uint32_t) * slots * ix.vis_words + (int64_t)sizeof(int32_t) * slots * ix.clear_cap;
-    }
-    DRM_HIP_CHECK(hipMalloc(&ix.counter, 4 * sizeof(uint32_t)));
-    DRM_HIP_CHECK(hipMemset(ix.counter, 0, 4 * sizeof(uint32_t)));
-    const int cap = std::max(ix.log_cap_req, 128 + 128); // what the lean kernel asks for at ef = 128
-    if (ix.log)
-        DRM_HIP_CHECK(hipFree(ix.log));
-    DRM_HIP_CHECK(hipMalloc(&ix.log, sizeof(uint64_t) * (size_t)slots * (size_t)cap));
-    ix.log_cap = cap;
-    ix.log_slots = slots;
-    ix.device_bytes += (int64_t)sizeof(uint64_t) * slots * cap;
-}
-
-void check_search_errors(DeviceIndex &ix)
-{
-    if (!ix.counter)
-        return;
-    uint32_t c[4] = {0, 0, 0, 0};
-    DRM_HIP_CHECK(hipMemcpy(c, ix.counter, sizeof(c), hipMemcpyDeviceToHost));
-    if (c[3]) {
-        DRM_HIP_CHECK(hipMemset(ix.counter + 3, 0, sizeof(uint32_t))); // reported once
-        throw Error(DRM_ERR_INTERNAL, std::to_string(c[3]) + " queries exceeded the search's hop bound or waves their "
-                                                             "work-item bound (DESIGN.md sec. 4.1): search state broken");
-    }
-}
-
-int64_t search_hop_bound(const DeviceIndex &ix) { return ix.hop_bound > 0 ? std::min(ix.hop_bound, ix.ntotal) : ix.ntotal; }
-int64_t search_item_bound(const DeviceIndex &ix, int64_t n) { return ix.item_bound > 0 ? std::min(ix.item_bound, n) : n; }
-
-void launch_hnsw_search(DeviceIndex &ix, const float *d_x, int64_t n, int k, int ef, float *d_D, int64_t *d_I,
-                        int32_t *d_ndis, int32_t *d_nhops, int32_t *d_nhops_upper, hipStream_t stream)
-{
-    if (n <= 0)
-        return;
     if (k < 1 || k > 1024)
         throw Error(DRM_ERR_UNSUPPORTED, "k must be in [1, 1024] on the GPU path, got " + std::to_string(k));
-    if (ef < 1)
-        ef = 1;
-    const int efc = std::max(ef, k);
     if (ix.deg0 > 64)
         throw Error(DRM_ERR_UNSUPPORTED, "level-0 degree 2*M_hnsw must be <= 64 on the GPU path");
     for (int l = 1; l < ix.n_levels; ++l)
@@ -784,57 +739,119 @@ void launch_hnsw_search(DeviceIndex &ix, const float *d_x, int64_t n, int k, int
             throw Error(DRM_ERR_UNSUPPORTED, "upper-level degree must be <= 64");
     if ((size_t)ix.pq_M * (size_t)ix.ksub > 16384)
         throw Error(DRM_ERR_UNSUPPORTED, "PQ LUT M*2^nbits must be <= 16384 entries (64 KB LDS)");
+    const int R = (efc + 63) / 64;
+    if ((R > 8 || ix.force_lds_kernel) && efc > 4096) // the LDS-heap kernel's own limit
+        throw Error(DRM_ERR_UNSUPPORTED, "max(efSearch, k) must be <= 4096 on the GPU path");
+}
 
-    int kpad = 64;
-    while (kpad < k)
-        kpad <<= 1;
-    const int R = (std::max(efc, k) + 63) / 64;
-    if (R > 8 || ix.force_lds_kernel) { // large ef / k: LDS-heap kernel
-        launch_hnsw_search_lds(ix, d_x, n, k, ef, d_D, d_I, d_ndis, d_nhops, d_nhops_upper, stream);
+struct SearchPlan {
+    enum Kernel { kLean, kRegHeap, kLdsHeap } kernel;
+    int R;            // kRegHeap: the instantiation, 1, 2, 4 or 8 (64 R heap slots in registers)
+    bool fast8;       // PQ 8 x 8: one 8-byte code load per distance
+    int kpad;         // k rounded up to a power of two >= 64 (the LDS kernel's output sort)
+    size_t lds;       // LDS bytes per wave (dynamic, except the lean kernel's LUT, which is static)
+    int per_cu;       // resident waves per CU
+    int slots;        // workgroups of this launch
+    int full_slots;   // of a full grid, what the workspace is sized for
+    bool need_bitmap; // false for the lean kernel without exact statistics: its heap is the visited set
+    int log_cap;      // push-log entries per slot (read by the lean kernel only)
+};
+
+SearchPlan plan_search(const DeviceIndex &ix, int64_t n, int k, int ef, int cus)
+{
+    SearchPlan p{};
+    const int efc = std::max(ef, k);
+    const int R = (efc + 63) / 64;
+    p.fast8 = ix.pq_M == 8 && ix.pq_nbits == 8 && ix.code_size == 8;
+    p.kpad = 64;
+    while (p.kpad < k)
+        p.kpad <<= 1;
+    if (R > 8 || ix.force_lds_kernel) { // large ef / k: heaps in LDS (hnsw_search_lds.hip)
+        p.kernel = SearchPlan::kLdsHeap;
+        // LUT, padded query, candidate heap, result heap / sort image, one expansion's scratch: 8-byte entries
+        p.lds = lut_bytes(ix) + sizeof(float) * (size_t)((ix.d + 3) & ~3) +
+                8 * ((size_t)((efc + 1) & ~1) + (size_t)p.kpad + 64);
+        p.per_cu = std::max(1, std::min(16, (int)(kLdsPerCu / p.lds)));
+    } else {
+        p.kernel = ix.use_fast && hnsw_pq_fast_supported(ix, k, efc) ? SearchPlan::kLean : SearchPlan::kRegHeap;
+        p.R = R <= 2 ? R : R <= 4 ? 4 : 8;
+        p.lds = lut_bytes(ix);
+        p.per_cu = lut_waves_per_cu(ix);
+    }
+    p.slots = (int)std::min<int64_t>(n, (int64_t)cus * p.per_cu);
+    p.full_slots = (int)std::min<int64_t>((int64_t)cus * p.per_cu, 1 << 20);
+    p.need_bitmap = p.kernel != SearchPlan::kLean || ix.exact_stats; // the lean kernel: only to count faiss's ndis
+    p.log_cap = search_log_cap(ix, efc);
+    return p;
+}
+
+// Visited bitmaps and clear lists for `slots` workgroups: regrown, to max(slots, full_slots), when there are fewer or
+// the index size changed the words per bitmap. device_bytes goes down by what is freed and up by what is allocated.
+void ensure_visited(DeviceIndex &ix, int slots, int full_slots)
+{
+    const int64_t words = std::max<int64_t>((ix.ntotal + 31) / 32, 1);
+    if (slots <= ix.n_slots && words == ix.vis_words)
         return;
+    if (ix.visited) {
+        DRM_HIP_CHECK(hipFree(ix.visited));
+        ix.device_bytes -= (int64_t)sizeof(uint32_t) * ix.n_slots * ix.vis_words;
     }
-    const size_t lds = sizeof(float) * (size_t)ix.pq_M * ix.ksub; // the LUT
-    if (lds > 160 * 1024)
-        throw Error(DRM_ERR_UNSUPPORTED, "search workspace does not fit in LDS");
-
-    int cus = 0;
-    DRM_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ix.device));
-    int per_cu = std::max(1, std::min(ix.waves_per_cu, (int)((160 * 1024) / lds)));
-    int slots = (int)std::min<int64_t>(n, (int64_t)cus * per_cu);
-    // (re)allocate per-slot workspace: the lean kernel needs the bitmap only to count faiss's ndis
-    const bool fast_path = ix.use_fast && hnsw_pq_fast_supported(ix, k, efc);
-    const bool need_bitmap = !fast_path || ix.exact_stats;
-    const int64_t words = (ix.ntotal + 31) / 32;
-    if (need_bitmap && (slots > ix.n_slots || words != ix.vis_words)) {
-        if (ix.visited) {
-            DRM_HIP_CHECK(hipFree(ix.visited));
-            ix.device_bytes -= (int64_t)sizeof(uint32_t) * ix.n_slots * ix.vis_words;
-        }
-        if (ix.clear_list) {
-            DRM_HIP_CHECK(hipFree(ix.clear_list));
-            ix.device_bytes -= (int64_t)sizeof(int32_t) * ix.n_slots * ix.clear_cap;
-        }
-        ix.visited = nullptr;
-        ix.clear_list = nullptr;
-        const int alloc_slots = std::max(slots, (int)std::min<int64_t>((int64_t)cus * per_cu, 1 << 20));
-        ix.vis_words = std::max<int64_t>(words, 1);
-        ix.clear_cap = 16384;
-        size_t free_b = 0, total_b = 0;
-        DRM_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-        const size_t need_b = sizeof(uint32_t) * (size_t)alloc_slots * (size_t)ix.vis_words +
-                              sizeof(int32_t) * (size_t)alloc_slots * (size_t)ix.clear_cap;
-        if (need_b > free_b)
-            throw Error(DRM_ERR_UNSUPPORTED, "the search's visited bitmaps need " + std::to_string(need_b >> 20) +
-                                                 " MiB of device memory, " + std::to_string(free_b >> 20) + " MiB free");
-        DRM_HIP_CHECK(malloc_big((void **)&ix.visited, sizeof(uint32_t) * (size_t)alloc_slots * (size_t)ix.vis_words, kBigVisited));
-        DRM_HIP_CHECK(hipMemset(ix.visited, 0, sizeof(uint32_t) * (size_t)alloc_slots * (size_t)ix.vis_words));
-        DRM_HIP_CHECK(hipMalloc(&ix.clear_list, sizeof(int32_t) * (size_t)alloc_slots * (size_t)ix.clear_cap));
-        ix.n_slots = alloc_slots;
-        ix.device_bytes += (int64_t)(need_b);
+    if (ix.clear_list) {
+        DRM_HIP_CHECK(hipFree(ix.clear_list));
+        ix.device_bytes -= (int64_t)sizeof(int32_t) * ix.n_slots * ix.clear_cap;
     }
-    if (!ix.counter)
-        DRM_HIP_CHECK(hipMalloc(&ix.counter, 4 * sizeof(uint32_t)));
+    ix.visited = nullptr;
+    ix.clear_list = nullptr;
+    ix.n_slots = 0; // nothing is held, or counted, until both allocations below have succeeded
+    ix.vis_words = 0;
+    const int alloc_slots = std::max(slots, full_slots);
+    const int32_t clear_cap = 16384;
+    const size_t vis_b = sizeof(uint32_t) * (size_t)alloc_slots * (size_t)words;
+    const size_t clr_b = sizeof(int32_t) * (size_t)alloc_slots * (size_t)clear_cap;
+    size_t free_b = 0, total_b = 0;
+    DRM_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+    if (vis_b + clr_b > free_b)
+        throw Error(DRM_ERR_UNSUPPORTED, "the search's visited bitmaps need " + std::to_string((vis_b + clr_b) >> 20) +
+                                             " MiB of device memory, " + std::to_string(free_b >> 20) + " MiB free");
+    DRM_HIP_CHECK(malloc_big((void **)&ix.visited, vis_b, kBigVisited));
+    DRM_HIP_CHECK(hipMemset(ix.visited, 0, vis_b));
+    DRM_HIP_CHECK(hipMalloc(&ix.clear_list, clr_b));
+    ix.n_slots = alloc_slots;
+    ix.vis_words = words;
+    ix.clear_cap = clear_cap;
+    ix.device_bytes += (int64_t)(vis_b + clr_b);
+}
 
+// The lean kernel's push log: `cap` entries for each of at least `slots` workgroups (it never loses slots).
+void ensure_log(DeviceIndex &ix, int slots, int cap)
+{
+    if (ix.log && ix.log_cap == cap && ix.log_slots >= slots)
+        return;
+    const int need = std::max(ix.log_slots, slots);
+    if (ix.log) {
+        DRM_HIP_CHECK(hipFree(ix.log));
+        ix.device_bytes -= (int64_t)sizeof(uint64_t) * ix.log_slots * ix.log_cap;
+    }
+    ix.log = nullptr;
+    ix.log_slots = 0;
+    DRM_HIP_CHECK(hipMalloc(&ix.log, sizeof(uint64_t) * (size_t)need * (size_t)cap));
+    ix.log_cap = cap;
+    ix.log_slots = need;
+    ix.device_bytes += (int64_t)sizeof(uint64_t) * need * cap;
+}
+
+// Work-queue head and error count: four words (not counted in device_bytes), zeroed before every launch.
+void ensure_counter(DeviceIndex &ix)
+{
+    if (ix.counter)
+        return;
+    DRM_HIP_CHECK(hipMalloc(&ix.counter, 4 * sizeof(uint32_t)));
+    DRM_HIP_CHECK(hipMemset(ix.counter, 0, 4 * sizeof(uint32_t)));
+}
+
+SearchArgs make_search_args(const DeviceIndex &ix, const SearchPlan &p, const float *d_x, int64_t n, int k, int ef,
+                            float *d_D, int64_t *d_I, int32_t *d_ndis, int32_t *d_nhops, int32_t *d_nhops_upper)
+{
     SearchArgs a{};
     a.x = d_x;
     a.n = n;
@@ -857,8 +874,8 @@ void launch_hnsw_search(DeviceIndex &ix, const float *d_x, int64_t n, int k, int
     a.ntotal = ix.ntotal;
     a.k = k;
     a.efSearch = ef;
-    a.ef = efc;
-    a.kpad = kpad;
+    a.ef = std::max(ef, k);
+    a.kpad = p.kpad;
     a.D = d_D;
     a.I = d_I;
     a.ndis = d_ndis;
@@ -873,57 +890,107 @@ void launch_hnsw_search(DeviceIndex &ix, const float *d_x, int64_t n, int k, int
     a.hop_bound = search_hop_bound(ix);
     a.item_bound = search_item_bound(ix, n);
     a.check_dups = ix.has_dup_links;
+    a.x_aligned16 = ((uintptr_t)d_x % 16) == 0;
     a.stamps = ix.stamps;
     a.trace = ix.trace;
-    a.x_aligned16 = ((uintptr_t)d_x % 16) == 0;
+    // read by the lean kernel only
+    a.log = ix.log;
+    a.log_cap = ix.log_cap;
+    a.rows = ix.rows;
+    a.row_words = ix.row_words;
+    a.upper_codes = ix.upper_codes;
+    a.exact_stats = ix.exact_stats;
+    return a;
+}
 
-    const bool fast8 = (ix.pq_M == 8 && ix.pq_nbits == 8 && ix.code_size == 8);
-    if (fast_path) {
-        // the lean kernel (hnsw_pq_fast.hip); k == ef logs accepted pushes per slot
-        // a compacted log holds <= k <= ef entries; then up to 64 staged evictions, or the ef heap entries at the end
-        const int cap = std::max(ix.log_cap_req, efc + std::max(efc, 64));
-        const int need = std::max(ix.log_slots, slots);
-        if (!ix.log || ix.log_cap != cap || ix.log_slots < need) {
-            if (ix.log) {
-                DRM_HIP_CHECK(hipFree(ix.log));
-                ix.device_bytes -= (int64_t)sizeof(uint64_t) * ix.log_slots * ix.log_cap;
+// hnsw_pq_search_kernel<R, F8> for the plan's R; <2, true, true> is the diagnostic build with section timers
+template <bool F8> void launch_reg_heap(const SearchArgs &a, const SearchPlan &p, hipStream_t stream)
+{
+    const dim3 grid(p.slots), block(64);
+    switch (p.R) {
+    case 1: hipLaunchKernelGGL((hnsw_pq_search_kernel<1, F8>), grid, block, p.lds, stream, a); break;
+    case 2:
+        if constexpr (F8)
+            if (a.stamps) {
+                hipLaunchKernelGGL((hnsw_pq_search_kernel<2, true, true>), grid, block, p.lds, stream, a);
+                break;
             }
-            ix.log = nullptr;
-            DRM_HIP_CHECK(hipMalloc(&ix.log, sizeof(uint64_t) * (size_t)need * (size_t)cap));
-            ix.log_cap = cap;
-            ix.log_slots = need;
-            ix.device_bytes += (int64_t)sizeof(uint64_t) * need * cap;
-        }
-        a.log = ix.log;
-        a.log_cap = ix.log_cap;
-        a.rows = ix.rows;
-        a.row_words = ix.row_words;
-        a.upper_codes = ix.upper_codes;
-        a.exact_stats = ix.exact_stats;
-        DRM_HIP_CHECK(hipMemsetAsync(ix.counter, 0, 4 * sizeof(uint32_t), stream));
-        launch_hnsw_pq_fast(a, slots, ix.stamps != nullptr, stream);
-        return;
+        hipLaunchKernelGGL((hnsw_pq_search_kernel<2, F8>), grid, block, p.lds, stream, a);
+        break;
+    case 4: hipLaunchKernelGGL((hnsw_pq_search_kernel<4, F8>), grid, block, p.lds, stream, a); break;
+    default: hipLaunchKernelGGL((hnsw_pq_search_kernel<8, F8>), grid, block, p.lds, stream, a); break;
     }
-    DRM_HIP_CHECK(hipMemsetAsync(ix.counter, 0, 4 * sizeof(uint32_t), stream));
-#define DRM_LAUNCH_EXACT(RR, F8)                                                                               \
-    hipLaunchKernelGGL((hnsw_pq_search_kernel<RR, F8>), dim3(slots), dim3(64), lds, stream, a)
-#define DRM_LAUNCH_EXACT_R(F8)                                                                                 \
-    switch (R) {                                                                                                \
-    case 1: DRM_LAUNCH_EXACT(1, F8); break;                                                                     \
-    case 2: DRM_LAUNCH_EXACT(2, F8); break;                                                                     \
-    case 3: case 4: DRM_LAUNCH_EXACT(4, F8); break;                                                             \
-    default: DRM_LAUNCH_EXACT(8, F8); break;                                                                    \
-    }
-    if (fast8 && ix.stamps && R == 2) {
-        hipLaunchKernelGGL((hnsw_pq_search_kernel<2, true, true>), dim3(slots), dim3(64), lds, stream, a);
-    } else if (fast8) {
-        DRM_LAUNCH_EXACT_R(true)
-    } else {
-        DRM_LAUNCH_EXACT_R(false)
-    }
-#undef DRM_LAUNCH_EXACT_R
-#undef DRM_LAUNCH_EXACT
     DRM_HIP_CHECK(hipGetLastError());
+}
+
+} // namespace
+
+// Per-slot search workspace (visited bitmaps, clear lists, queue counters, the lean kernel's push log)
+// for a full-occupancy grid, allocated once at index load so that no search pays for it (at C5 a bitmap
+// workspace is 32 GB). Searches that need more (other LUT sizes, larger logs) still grow it. The lean kernel
+// keeps no visited table: with inline rows the bitmap waits for a search that needs it (another kernel, or
+// exact statistics).
+void reserve_search_scratch(DeviceIndex &ix)
+{
+    int cus = 0;
+    DRM_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ix.device));
+    const size_t lut = lut_bytes(ix);
+    if (lut == 0 || lut > kLdsPerCu)
+        return;
+    const int slots = cus * lut_waves_per_cu(ix);
+    if (!ix.rows)
+        ensure_visited(ix, slots, slots);
+    ensure_counter(ix);
+    ensure_log(ix, slots, search_log_cap(ix, 128)); // what the lean kernel asks for at ef = 128
+}
+
+void check_search_errors(DeviceIndex &ix)
+{
+    if (!ix.counter)
+        return;
+    uint32_t c[4] = {0, 0, 0, 0};
+    DRM_HIP_CHECK(hipMemcpy(c, ix.counter, sizeof(c), hipMemcpyDeviceToHost));
+    if (c[3]) {
+        DRM_HIP_CHECK(hipMemset(ix.counter + 3, 0, sizeof(uint32_t))); // reported once
+        throw Error(DRM_ERR_INTERNAL, std::to_string(c[3]) + " queries exceeded the search's hop bound or waves their "
+                                                             "work-item bound (DESIGN.md sec. 4.1): search state broken");
+    }
+}
+
+int64_t search_hop_bound(const DeviceIndex &ix) { return ix.hop_bound > 0 ? std::min(ix.hop_bound, ix.ntotal) : ix.ntotal; }
+int64_t search_item_bound(const DeviceIndex &ix, int64_t n) { return ix.item_bound > 0 ? std::min(ix.item_bound, n) : n; }
+
+// plan, ensure, fill, launch
+void launch_hnsw_search(DeviceIndex &ix, const float *d_x, int64_t n, int k, int ef, float *d_D, int64_t *d_I,
+                        int32_t *d_ndis, int32_t *d_nhops, int32_t *d_nhops_upper, hipStream_t stream)
+{
+    if (n <= 0)
+        return;
+    if (ef < 1)
+        ef = 1;
+    check_search_limits(ix, k, std::max(ef, k));
+    int cus = 0;
+    DRM_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ix.device));
+    const SearchPlan p = plan_search(ix, n, k, ef, cus);
+    if (p.lds > kLdsPerCu)
+        throw Error(DRM_ERR_UNSUPPORTED, "search workspace does not fit in LDS");
+
+    if (p.need_bitmap)
+        ensure_visited(ix, p.slots, p.full_slots);
+    if (p.kernel == SearchPlan::kLean)
+        ensure_log(ix, p.slots, p.log_cap); // k == ef logs accepted pushes per slot
+    ensure_counter(ix);
+
+    const SearchArgs a = make_search_args(ix, p, d_x, n, k, ef, d_D, d_I, d_ndis, d_nhops, d_nhops_upper);
+    DRM_HIP_CHECK(hipMemsetAsync(ix.counter, 0, 4 * sizeof(uint32_t), stream)); // queue head and error count
+    if (p.kernel == SearchPlan::kLean)
+        launch_hnsw_pq_fast(a, p.slots, ix.stamps != nullptr, stream);
+    else if (p.kernel == SearchPlan::kLdsHeap)
+        launch_hnsw_pq_lds(a, p.slots, p.lds, p.fast8, stream);
+    else if (p.fast8)
+        launch_reg_heap<true>(a, p, stream);
+    else
+        launch_reg_heap<false>(a, p, stream);
 }
 
 } // namespace drm

@@ -1,26 +1,9 @@
-// deepreadmapper_amd/csrc/hnsw_search_lds.hip -- general-size fallback of the HNSW-PQ search kernel
-// (heaps in LDS, replayed on lane 0), used when max(efSearch, k) > 512. Same semantics and results as
-// hnsw_search.hip; see that file for the fast register-resident path.
-//
-// Original notes:
-//
-// Replaces the hot loop behind faiss_search (src/hnswpq/search.cpp:39-40): faiss
-// IndexHNSW::search -> HNSW::search (greedy upper levels + search_from_candidates at level 0)
-// with PQDistanceComputer (ADC over an 8 x 256 LUT) [upstream faiss >= 1.8, restated in
-// oracle/drm_oracle.c]. Results are bit-identical to that restatement: same ids, same fp32
-// distances (same op order, no FMA contraction), same ndis / nhops.
-//
-// Mapping (DESIGN.md "HNSW kernel"):
-//   * one 64-lane wave = one query; persistent grid of `n_slots` one-wave workgroups pulling
-//     query indices from an atomic work queue (every wave exits once the queue is drained);
-//   * LDS per wave: the query's PQ LUT (M*ksub f32 = 8 KB), the MinimaxHeap (ef x {f32,i32}),
-//     the k-result heap, the query vector and a 64-entry scratch for one expansion;
-//   * one level-0 neighbour row (2*M_hnsw int32 = 128 B) is one coalesced load, lane j = link j;
-//   * visited set = a per-slot bitmap in HBM (ntotal bits), test-and-set with one atomicOr per
-//     link, cleared after the query from the list of bits it set (exact, no false positives);
-//   * pop_min and count_below are wave-parallel (64-bit key min-reduction / ballot+popcount);
-//     heap pushes/pops and result-heap updates replay faiss's exact array layout on lane 0,
-//     because the traversal order under equal distances depends on it.
+// deepreadmapper_amd/csrc/hnsw_search_lds.hip -- the HNSW-PQ search with its heaps in LDS, for any max(efSearch, k)
+// up to 4096: launch_hnsw_search (hnsw_search.hip) picks it when the heaps pass the 512 register slots of
+// hnsw_pq_search_kernel<8>, or when forced (DRM_SEARCH_LDS_KERNEL=1). Same semantics and results as that kernel, and
+// the same pq_common.h for the distance, the greedy descent and the wave reductions. What differs: the query is staged
+// in LDS for the LUT build, the candidate and result heaps are faiss's arrays of (f32 distance, i32 id) in LDS,
+// replayed on lane 0 (pop_min and count_below stay wave-parallel), and the output is a bitonic sort in LDS.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,6 +11,7 @@
 #include <cmath>
 
 #include "drm_device.h"
+#include "pq_common.h"
 
 #pragma clang fp contract(off)
 
@@ -39,32 +23,7 @@ struct DI {
     int32_t i;
 };
 
-__device__ __forceinline__ uint32_t ord32(float f)
-{
-    uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        uint32_t lo = __shfl_xor((uint32_t)v, off, 64);
-        uint32_t hi = __shfl_xor((uint32_t)(v >> 32), off, 64);
-        uint64_t o = ((uint64_t)hi << 32) | lo;
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
-
-__device__ __forceinline__ int prefix_count(uint64_t mask, int lane)
-{
-    return __popcll(mask & ((lane == 0) ? 0ull : (~0ull >> (64 - lane))));
-}
-
-// faiss::CMax<float, TI>::cmp2
+// faiss::CMax<float, TI>::cmp2 on the distances themselves (pq_common.h's compares their ord32 images)
 __device__ __forceinline__ bool cmp2(float v1, float v2, int32_t i1, int32_t i2)
 {
     return (v1 > v2) || ((v1 == v2) && (i1 > i2));
@@ -136,41 +95,6 @@ __device__ void heap_replace_top(DI *h, int k, float val, int32_t id)
     h[i - 1] = DI{val, id};
 }
 
-// PQ ADC distance of node v: sequential fp32 sum over sub-quantizers starting from 0
-// (distance_single_code / distance_four_codes for M < 16) [upstream faiss].
-template <bool FAST8>
-__device__ __forceinline__ float pq_distance(const SearchArgs &a, const float *lut, int32_t v)
-{
-    float r = 0.0f;
-    if (FAST8) { // M == 8, nbits == 8: one 8-byte code load
-        const uint2 c = *reinterpret_cast<const uint2 *>(a.codes + (size_t)v * 8);
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-            r = __fadd_rn(r, lut[m * 256 + ((c.x >> (8 * m)) & 255u)]);
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-            r = __fadd_rn(r, lut[(m + 4) * 256 + ((c.y >> (8 * m)) & 255u)]);
-        return r;
-    }
-    const uint8_t *code = a.codes + (size_t)v * a.code_size;
-    for (int m = 0; m < a.M; ++m) {
-        uint32_t idx;
-        if (a.nbits == 8) {
-            idx = code[m];
-        } else {
-            uint32_t bitpos = (uint32_t)m * (uint32_t)a.nbits;
-            uint32_t byte = bitpos >> 3, shift = bitpos & 7;
-            uint32_t need = shift + (uint32_t)a.nbits;
-            uint32_t acc = 0;
-            for (uint32_t b = 0; b * 8 < need; ++b)
-                acc |= (uint32_t)code[byte + b] << (8 * b);
-            idx = (acc >> shift) & ((1u << a.nbits) - 1u);
-        }
-        r = __fadd_rn(r, lut[m * a.ksub + (int)idx]);
-    }
-    return r;
-}
-
 template <bool FAST8>
 __global__ __launch_bounds__(64) void hnsw_pq_search_lds_kernel(SearchArgs a)
 {
@@ -197,7 +121,6 @@ __global__ __launch_bounds__(64) void hnsw_pq_search_lds_kernel(SearchArgs a)
             break;
         }
 
-        int32_t ndis = 0, nhops = 0;
         // --- HeapBlockResultHandler::begin: heapify k x (+inf, -1)
         for (int j = lane; j < a.k; j += 64)
             res[j] = DI{INFINITY, -1};
@@ -232,37 +155,11 @@ __global__ __launch_bounds__(64) void hnsw_pq_search_lds_kernel(SearchArgs a)
         __syncthreads();
 
         // --- greedy descent on levels max_level .. 1 (greedy_update_nearest)
-        int32_t nearest = a.entry_point;
-        float d_nearest = pq_distance<FAST8>(a, lut, nearest);
-        for (int level = a.max_level; level >= 1; --level) {
-            const int cnt = a.cum[level + 1] - a.cum[level];
-            for (;;) {
-                const int32_t prev = nearest;
-                const uint32_t base = a.upper_off[nearest] + (uint32_t)(a.cum[level] - a.cum[1]);
-                int32_t v = (lane < cnt) ? a.upper_nbr[base + lane] : -1;
-                const uint64_t neg = __ballot(lane < cnt && v < 0);
-                const int nvalid = neg ? (__ffsll((unsigned long long)neg) - 1) : cnt;
-                float dd = INFINITY;
-                if (lane < nvalid)
-                    dd = pq_distance<FAST8>(a, lut, v);
-                ndis += nvalid;
-                nhops += 1;
-                // sequential `if (dis < d_nearest)` in link order == first lane holding the minimum
-                uint64_t key = (lane < nvalid) ? (((uint64_t)ord32(dd) << 32) | (uint32_t)lane) : ~0ull;
-                key = wave_min_u64(key);
-                if (key != ~0ull) {
-                    const int bl = (int)(key & 63);
-                    const float bd = __shfl(dd, bl, 64);
-                    const int32_t bv = __shfl(v, bl, 64);
-                    if (bd < d_nearest) {
-                        d_nearest = bd;
-                        nearest = bv;
-                    }
-                }
-                if (nearest == prev)
-                    break;
-            }
-        }
+        int32_t nearest;
+        uint32_t dn;
+        int ndis, nhops;
+        greedy_upper<FAST8>(a, lut, lane, nearest, dn, ndis, nhops);
+        const float d_nearest = unord32(dn); // the heaps hold the distance itself: ord32's exact inverse
 
         // --- level 0: MinimaxHeap candidates(ef); push(nearest); seed result + visited
         int kc = 1, nvalid = 1;
@@ -301,7 +198,7 @@ __global__ __launch_bounds__(64) void hnsw_pq_search_lds_kernel(SearchArgs a)
                     best = key < best ? key : best;
                 }
             }
-            best = wave_min_u64(best);
+            best = wave_min_u64_lanes(best); // not the wave-uniform form: 1.5 % slower here
             const int imin = (int)(0xFFFFFFFFu - (uint32_t)best);
             const DI pm = cand[imin];
             const float d0 = pm.d;
@@ -340,11 +237,11 @@ __global__ __launch_bounds__(64) void hnsw_pq_search_lds_kernel(SearchArgs a)
             }
             const uint64_t fm = __ballot(fresh);
             const int nf = __popcll(fm);
-            const int pos = prefix_count(fm, lane);
+            const int pos = __popcll(fm & lanes_below(lane));
             if (fresh) {
                 if (clear_n + pos < a.clear_cap)
                     clr[clear_n + pos] = v1;
-                const float dd = pq_distance<FAST8>(a, lut, v1);
+                const float dd = pq_distance_code<FAST8>(a, lut, v1, load_code8<FAST8>(a, v1));
                 nb[pos] = DI{dd, v1};
             }
             clear_n += nf;
@@ -406,9 +303,7 @@ __global__ __launch_bounds__(64) void hnsw_pq_search_lds_kernel(SearchArgs a)
                 a.D[q * a.k + j] = INFINITY;
                 a.I[q * a.k + j] = -1;
             } else {
-                const uint32_t o = (uint32_t)(key >> 32);
-                const uint32_t u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
-                a.D[q * a.k + j] = __uint_as_float(u);
+                a.D[q * a.k + j] = unord32((uint32_t)(key >> 32));
                 a.I[q * a.k + j] = (int64_t)(uint32_t)key;
             }
         }
@@ -436,109 +331,12 @@ __global__ __launch_bounds__(64) void hnsw_pq_search_lds_kernel(SearchArgs a)
 
 } // namespace
 
-void launch_hnsw_search_lds(DeviceIndex &ix, const float *d_x, int64_t n, int k, int ef, float *d_D, int64_t *d_I,
-                        int32_t *d_ndis, int32_t *d_nhops, int32_t *d_nhops_upper, hipStream_t stream)
+void launch_hnsw_pq_lds(const SearchArgs &a, int slots, size_t lds_bytes, bool fast8, hipStream_t stream)
 {
-    if (n <= 0)
-        return;
-    if (k < 1 || k > 1024)
-        throw Error(DRM_ERR_UNSUPPORTED, "k must be in [1, 1024] on the GPU path, got " + std::to_string(k));
-    if (ef < 1)
-        ef = 1;
-    const int efc = std::max(ef, k);
-    if (efc > 4096)
-        throw Error(DRM_ERR_UNSUPPORTED, "max(efSearch, k) must be <= 4096 on the GPU path");
-    if (ix.deg0 > 64)
-        throw Error(DRM_ERR_UNSUPPORTED, "level-0 degree 2*M_hnsw must be <= 64 on the GPU path");
-    for (int l = 1; l < ix.n_levels; ++l)
-        if (ix.cum[l + 1] - ix.cum[l] > 64)
-            throw Error(DRM_ERR_UNSUPPORTED, "upper-level degree must be <= 64");
-    if ((size_t)ix.pq_M * (size_t)ix.ksub > 16384)
-        throw Error(DRM_ERR_UNSUPPORTED, "PQ LUT M*2^nbits must be <= 16384 entries (64 KB LDS)");
-
-    int kpad = 64;
-    while (kpad < k)
-        kpad <<= 1;
-    const size_t lds = sizeof(float) * (size_t)ix.pq_M * ix.ksub + sizeof(float) * (size_t)((ix.d + 3) & ~3) +
-                       sizeof(DI) * (size_t)((efc + 1) & ~1) + sizeof(DI) * (size_t)kpad + sizeof(DI) * 64;
-    if (lds > 160 * 1024)
-        throw Error(DRM_ERR_UNSUPPORTED, "search workspace does not fit in LDS");
-
-    int cus = 0;
-    DRM_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ix.device));
-    int per_cu = std::max(1, std::min(16, (int)((160 * 1024) / lds)));
-    int slots = (int)std::min<int64_t>(n, (int64_t)cus * per_cu);
-    // (re)allocate per-slot workspace
-    const int64_t words = (ix.ntotal + 31) / 32;
-    if (slots > ix.n_slots || words != ix.vis_words) {
-        if (ix.visited) {
-            DRM_HIP_CHECK(hipFree(ix.visited));
-            ix.device_bytes -= (int64_t)sizeof(uint32_t) * ix.n_slots * ix.vis_words;
-        }
-        if (ix.clear_list) {
-            DRM_HIP_CHECK(hipFree(ix.clear_list));
-            ix.device_bytes -= (int64_t)sizeof(int32_t) * ix.n_slots * ix.clear_cap;
-        }
-        ix.visited = nullptr;
-        ix.clear_list = nullptr;
-        const int alloc_slots = std::max(slots, (int)std::min<int64_t>((int64_t)cus * per_cu, 1 << 20));
-        ix.vis_words = std::max<int64_t>(words, 1);
-        ix.clear_cap = 16384;
-        DRM_HIP_CHECK(malloc_big((void **)&ix.visited, sizeof(uint32_t) * (size_t)alloc_slots * (size_t)ix.vis_words, kBigVisited));
-        DRM_HIP_CHECK(hipMemset(ix.visited, 0, sizeof(uint32_t) * (size_t)alloc_slots * (size_t)ix.vis_words));
-        DRM_HIP_CHECK(hipMalloc(&ix.clear_list, sizeof(int32_t) * (size_t)alloc_slots * (size_t)ix.clear_cap));
-        ix.n_slots = alloc_slots;
-        ix.device_bytes += (int64_t)sizeof(uint32_t) * alloc_slots * ix.vis_words +
-                           (int64_t)sizeof(int32_t) * alloc_slots * ix.clear_cap; // as launch_hnsw_search accounts for it
-    }
-    if (!ix.counter)
-        DRM_HIP_CHECK(hipMalloc(&ix.counter, 4 * sizeof(uint32_t)));
-
-    SearchArgs a{};
-    a.x = d_x;
-    a.n = n;
-    a.d = ix.d;
-    a.M = ix.pq_M;
-    a.nbits = ix.pq_nbits;
-    a.ksub = ix.ksub;
-    a.dsub = ix.dsub;
-    a.code_size = ix.code_size;
-    a.centroids = ix.centroids;
-    a.codes = ix.codes;
-    a.nbr0 = ix.nbr0;
-    a.deg0 = ix.deg0;
-    a.upper_off = ix.upper_off;
-    a.upper_nbr = ix.upper_nbr;
-    for (int l = 0; l <= kMaxLevels; ++l)
-        a.cum[l] = ix.cum[l];
-    a.max_level = ix.max_level;
-    a.entry_point = ix.entry_point;
-    a.ntotal = ix.ntotal;
-    a.k = k;
-    a.efSearch = ef;
-    a.ef = efc;
-    a.kpad = kpad;
-    a.D = d_D;
-    a.I = d_I;
-    a.ndis = d_ndis;
-    a.nhops = d_nhops;
-    a.nhops_upper = d_nhops_upper;
-    a.visited = ix.visited;
-    a.vis_words = ix.vis_words;
-    a.clear_list = ix.clear_list;
-    a.clear_cap = ix.clear_cap;
-    a.counter = ix.counter;
-    a.errors = ix.counter + 3;
-    a.hop_bound = search_hop_bound(ix);
-    a.item_bound = search_item_bound(ix, n);
-    a.check_dups = ix.has_dup_links;
-
-    DRM_HIP_CHECK(hipMemsetAsync(ix.counter, 0, 4 * sizeof(uint32_t), stream)); // queue head and error count
-    const bool fast8 = (ix.pq_M == 8 && ix.pq_nbits == 8 && ix.code_size == 8);
     if (fast8)
-        hipLaunchKernelGGL(hnsw_pq_search_lds_kernel<true>, dim3(slots), dim3(64), lds, stream, a);
+        hipLaunchKernelGGL(hnsw_pq_search_lds_kernel<true>, dim3(slots), dim3(64), lds_bytes, stream, a);
     else
-        hipLaunchKernelGGL(hnsw_pq_search_lds_kernel<false>, dim3(slots), dim3(64), lds, stream, a);
+        hipLaunchKernelGGL(hnsw_pq_search_lds_kernel<false>, dim3(slots), dim3(64), lds_bytes, stream, a);
     DRM_HIP_CHECK(hipGetLastError());
 }
 

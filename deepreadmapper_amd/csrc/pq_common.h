@@ -1,5 +1,6 @@
 // deepreadmapper_amd/csrc/pq_common.h -- device helpers shared by the HNSW-PQ search kernels
-// (hnsw_search.hip: the general exact kernel; hnsw_pq_fast.hip: the lean ef <= 128 kernel).
+// (hnsw_search.hip: the general exact kernel; hnsw_search_lds.hip: its LDS-heap fallback; hnsw_pq_fast.hip: the lean
+// ef <= 128 kernel).
 // set_query / compute_distance_table, the PQ-ADC distance and greedy_update_nearest restate upstream
 // faiss (IndexPQ.cpp, ProductQuantizer.cpp, HNSW.cpp) with a fixed fp32 op order and no FMA; the
 // oracle (oracle/drm_oracle.c) uses the same order, so results are bit-identical to it.
@@ -30,7 +31,10 @@ __device__ __forceinline__ float unord32(uint32_t o)
     return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
 }
 
-__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v)
+// min over the 64 lanes by xor butterfly, left in every lane (to the compiler a per-lane value). The LDS-heap
+// kernel's pop_min takes it as it is: the wave-uniform form below made that kernel 1.5 % slower (154.0 -> 156.3 ms,
+// DESIGN.md sec. 4.2)
+__device__ __forceinline__ uint64_t wave_min_u64_lanes(uint64_t v)
 {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -39,6 +43,11 @@ __device__ __forceinline__ uint64_t wave_min_u64(uint64_t v)
         uint64_t o = ((uint64_t)hi << 32) | lo;
         v = o < v ? o : v;
     }
+    return v;
+}
+__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v)
+{
+    v = wave_min_u64_lanes(v);
     // every lane holds the minimum now; readfirstlane tells the compiler so (a shuffle result is a
     // divergent value to its uniformity analysis, and branches on it would become exec-masked)
     const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));

@@ -306,7 +306,7 @@ def test_full_reset_then_reuse_within_one_launch(fans, ramp, kernel, monkeypatch
     else:
         monkeypatch.setenv("DRM_SEARCH_FAST", "0")
         f, k, ef = fans[P.FAN_N_LDS], 10, 2048
-        lds = 4 * 8 * 256 + 4 * 128 + 8 * ((ef + 1) & ~1) + 8 * 64 + 8 * 64  # launch_hnsw_search_lds: LUT, query, heaps
+        lds = 4 * 8 * 256 + 4 * 128 + 8 * ((ef + 1) & ~1) + 8 * 64 + 8 * 64  # plan_search: LUT, query, heaps
         slots = cus * max(1, min(16, (160 * 1024) // lds))
         q = P.fan_queries(rng, slots + 101)
     assert len(q) > slots
@@ -429,8 +429,8 @@ def test_lut_size_limits(workdir, rnd4x12):
 # ------------------------------------------------------------------------------------------ g: one handle
 def test_one_handle_many_calls(built):
     """lean -> LDS -> general -> lean with exact statistics -> LDS with a larger k -> lean on one handle: the
-    visited bitmaps, the clear lists and the lean kernel's log are shared, and each launcher (re)allocates them
-    under its own condition."""
+    visited bitmaps, the clear lists and the lean kernel's log are shared, and ensure_visited / ensure_log
+    (re)allocate them for each kernel's own slot count."""
     f = built("8x8")
     ix = _open(f)
     _check(ix, f, 128, 128, ndis=False)
@@ -450,8 +450,8 @@ def test_one_handle_many_calls(built):
 def test_device_bytes_after_lds_reallocation(built):
     """Two handles that end with the same allocations report the same device_bytes. A: one LDS-heap search of more
     queries than CUs, which allocates the bitmaps and clear lists (an 8 x 8 index loads without them). B: first an
-    exact-statistics lean search at one wave per CU, which allocates CUs x 1 slots in launch_hnsw_search, then the
-    same LDS-heap search, which needs more slots and reallocates in launch_hnsw_search_lds."""
+    exact-statistics lean search at one wave per CU, which allocates CUs x 1 slots, then the same LDS-heap search,
+    which needs more slots and reallocates (both in ensure_visited)."""
     from deepreadmapper_amd._native import check, lib
     from deepreadmapper_amd.device import device_props
     f = built("8x8")
@@ -469,8 +469,120 @@ def test_device_bytes_after_lds_reallocation(built):
     check(lib().drm_index_set_search_waves(b.handle, 0))
     _check(b, f, 10, 600, q)
     words = (f["fx"].ntotal + 31) // 32
-    assert small - loaded == cus * (4 * words + 4 * 16384)  # launch_hnsw_search: CUs x 1 slots
+    assert small - loaded == cus * (4 * words + 4 * 16384)  # ensure_visited: CUs x 1 slots
     assert _device_bytes(a) > loaded and (_device_bytes(a) - loaded) % (4 * words + 4 * 16384) == 0
     assert _device_bytes(a) == _device_bytes(b)
     a.free()
     b.free()
+
+
+def _search_rows(ix, f, k, ef, n, ndis=True):
+    """One search of n queries (the fixture's 64, repeated) on an open handle; the first 64 rows against the oracle."""
+    q = np.ascontiguousarray(np.resize(f["q"], (n, f["q"].shape[1])))
+    D, I, _ = ix.search(q, k, ef)
+    Do, Io, _, _ = _oracle(f, f["q"], k, ef)
+    m = len(f["q"])
+    assert np.array_equal(I[:m], Io) and np.array_equal(D[:m].view(np.uint32), Do.view(np.uint32)), (k, ef, n)
+    assert np.array_equal(I[-m:], np.roll(Io, -((n - m) % m), axis=0)) and ix.search_errors() == 0, (k, ef, n)
+
+
+def test_device_bytes_is_path_independent(built, monkeypatch):
+    """device_bytes follows the workspace, whatever order the kernels came in. Three handles of the 8 x 8 index are
+    driven to the same final workspace: (i) LDS-heap, general, lean with exact statistics; (ii) the reverse order;
+    (iii) first a lean search at drm_index_set_search_waves(.., 1), then restored and as (i). Every search has more
+    queries than a full grid of any kernel has slots (CUs x 20), so each step's slot count is plan_search's full
+    grid: CUs x 11 for the LDS-heap kernel at ef = 600 (160 KB / 14,528 B of LDS), CUs x 20 for the other two, CUs
+    x 1 at one wave per CU. After each step the difference from the loaded value is exactly slots x (4 x words +
+    4 x 16384) for the bitmaps and clear lists plus 8 x slots x (cap - loaded cap) for the lean kernel's log, whose
+    cap is max(DRM_SEARCH_LOG_CAP, efc + max(efc, 64)): with the request at 64 the log is reallocated at 80 entries
+    for (10, 16) and back at 256 for (128, 128). Then a shape without inline rows (8 x 5): its loaded device_bytes is
+    its index arrays plus what reserve_search_scratch allocates, CUs x per_cu x (4 x words + 4 x 16384) of bitmaps
+    and clear lists and 8 x CUs x per_cu x cap of log -- cap = 256, the ef = 128 need, once the request
+    (DRM_SEARCH_LOG_CAP, 512 unless set) is no larger, and 512 by default."""
+    from deepreadmapper_amd._native import check, lib
+    from deepreadmapper_amd.device import device_props
+    cus = device_props()["cu_count"]
+    monkeypatch.delenv("DRM_SEARCH_WAVES_PER_CU", raising=False)
+    monkeypatch.setenv("DRM_SEARCH_LOG_CAP", "64")
+    f = built("8x8")
+    n = 20 * cus + 5
+    words = (f["fx"].ntotal + 31) // 32
+    per_slot = 4 * words + 4 * 16384
+    lds = 4 * 8 * 256 + 4 * 128 + 8 * ((600 + 1) & ~1) + 8 * 64 + 8 * 64  # plan_search: LUT, query, heaps
+    lds_per_cu = max(1, min(16, (160 * 1024) // lds))
+    assert lds_per_cu == 11
+    log80 = 8 * 20 * cus * (80 - 256)  # the log of a full grid, reallocated at cap 80 instead of the loaded 256
+
+    def lds_step(ix):
+        _search_rows(ix, f, 10, 600, n)
+
+    def general_step(ix):
+        _search_rows(ix, f, 300, 512, n)
+
+    def lean_step(ix, after_1016, after_128):
+        _search_rows(ix, f, 10, 16, n)
+        assert _device_bytes(ix) - loaded == after_1016
+        _search_rows(ix, f, 128, 128, n)
+        assert _device_bytes(ix) - loaded == after_128
+
+    handles = [_open(f) for _ in range(3)]
+    loaded = _device_bytes(handles[0])
+    for ix in handles:
+        assert _device_bytes(ix) == loaded
+        ix.set_exact_stats(True)
+    full = 20 * cus * per_slot
+    # (i)
+    a = handles[0]
+    lds_step(a)
+    assert _device_bytes(a) - loaded == lds_per_cu * cus * per_slot
+    general_step(a)
+    assert _device_bytes(a) - loaded == full
+    lean_step(a, full + log80, full)
+    # (ii)
+    b = handles[1]
+    lean_step(b, full + log80, full)
+    general_step(b)
+    assert _device_bytes(b) - loaded == full
+    lds_step(b)
+    assert _device_bytes(b) - loaded == full
+    # (iii)
+    c = handles[2]
+    check(lib().drm_index_set_search_waves(c.handle, 1))
+    _search_rows(c, f, 10, 16, n)
+    assert _device_bytes(c) - loaded == cus * per_slot + log80  # CUs x 1 slots of bitmaps; the log keeps its slots
+    check(lib().drm_index_set_search_waves(c.handle, 0))
+    lds_step(c)
+    assert _device_bytes(c) - loaded == lds_per_cu * cus * per_slot + log80
+    general_step(c)
+    assert _device_bytes(c) - loaded == full + log80
+    lean_step(c, full + log80, full)
+    for ix in handles:
+        d = _device_bytes(ix) - loaded
+        assert d == full and d % per_slot == 0
+    assert _device_bytes(a) == _device_bytes(b) == _device_bytes(c)
+    for ix in handles:  # statistics off releases the bitmaps and clear lists of an index with inline rows
+        ix.set_exact_stats(False)
+        assert _device_bytes(ix) == loaded
+        ix.free()
+
+    # no inline rows: the whole workspace is reserved at load
+    g = built("8x5")
+    fx = g["fx"]
+    cum = fx.cum_nneighbor_per_level
+    upper = int(sum(cum[lv] - cum[1] for lv in fx.levels if lv > 1))
+    arrays = (4 * len(fx.centroids) + len(fx.codes) + 4 * fx.ntotal * int(cum[1]) + 4 * fx.ntotal + 4 * max(upper, 1))
+    per_cu = max(1, min(20, (160 * 1024) // (4 * 8 * 32)))  # the LUT of 8 x 2^5 entries is the only LDS
+    gwords = (fx.ntotal + 31) // 32
+    for request, cap in (("256", 256), (None, 512)):
+        if request is None:
+            monkeypatch.delenv("DRM_SEARCH_LOG_CAP")
+        else:
+            monkeypatch.setenv("DRM_SEARCH_LOG_CAP", request)
+        ix = _open(g)
+        scratch = _device_bytes(ix) - arrays
+        print(f"8x5 loaded: request {request} scratch {scratch} = {cus} CUs x {per_cu} x ({4 * gwords} + {4 * 16384})"
+              f" + 8 x {cus} x {per_cu} x {cap}")
+        assert scratch == cus * per_cu * (4 * gwords + 4 * 16384) + 8 * cus * per_cu * cap, (request, cap)
+        _check(ix, g, 10, 16)
+        assert _device_bytes(ix) - arrays == scratch
+        ix.free()

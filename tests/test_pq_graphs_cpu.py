@@ -9,21 +9,21 @@ import pytest
 import pq_graphs as P
 from oracle import oracle as O
 
-# The thresholds of the launchers (deepreadmapper_amd/csrc):
-CLEAR_CAP = 16384   # hnsw_search.hip / hnsw_search_lds.hip `ix.clear_cap = 16384`: visited ids a query lists before
+# The thresholds of the launcher (deepreadmapper_amd/csrc/hnsw_search.hip):
+CLEAR_CAP = 16384   # ensure_visited `const int32_t clear_cap = 16384`: visited ids a query lists before
 #                     it resets its whole bitmap (`clear_n <= a.clear_cap` at the end of each kernel's query loop)
-R_MAX = 8           # hnsw_search.hip launch_hnsw_search `if (R > 8 || ix.force_lds_kernel)`, R = ceil(max(ef, k) / 64):
+R_MAX = 8           # plan_search `if (R > 8 || ix.force_lds_kernel)`, R = ceil(max(ef, k) / 64):
 LDS_ABOVE = 512     # ... so max(ef, k) > 512 goes to the LDS-heap kernel
 LEAN_EF_MAX = 128   # hnsw_pq_fast.hip hnsw_pq_fast_supported: `efc <= 128 && (k == efc || k <= 64)`, PQ 8 x 8 only
 LEAN_K_REG = 64
-K_MAX = 1024        # both launchers: `k < 1 || k > 1024`
-EFC_MAX = 4096      # hnsw_search_lds.hip launch_hnsw_search_lds: `efc > 4096`
-DEG_MAX = 64        # both launchers: `ix.deg0 > 64`, `ix.cum[l + 1] - ix.cum[l] > 64`
-LUT_MAX = 16384     # both launchers: `pq_M * ksub > 16384`
+K_MAX = 1024        # check_search_limits: `k < 1 || k > 1024`
+EFC_MAX = 4096      # check_search_limits, the LDS-heap kernel only: `efc > 4096`
+DEG_MAX = 64        # check_search_limits: `ix.deg0 > 64`, `ix.cum[l + 1] - ix.cum[l] > 64`
+LUT_MAX = 16384     # check_search_limits: `pq_M * ksub > 16384`
 
 
 def kernel_of(M_pq, nbits, k, ef, fast=True, force_lds=False):
-    """launch_hnsw_search's choice: "lean", "lds", or the general kernel's R instantiation (1, 2, 4, 8)."""
+    """plan_search's choice: "lean", "lds", or the general kernel's R instantiation (1, 2, 4, 8)."""
     efc = max(ef, k)
     assert 1 <= k <= K_MAX and efc <= EFC_MAX and M_pq * (1 << nbits) <= LUT_MAX
     R = (efc + 63) // 64
