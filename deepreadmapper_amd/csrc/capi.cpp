@@ -1363,6 +1363,16 @@ int32_t env_sw_band()
     check_sw_band(band);
     return band;
 }
+// the initial chunk size of a new handle's SW rerank (drm_refs_set_sw_chunk): DRM_SW_CHUNK, read once (unset: -1, the
+// library's plan), so that one library runs both launch orders in an A/B
+int64_t env_sw_chunk()
+{
+    static const int64_t chunk = [] {
+        const char *e = std::getenv("DRM_SW_CHUNK");
+        return e && *e ? (int64_t)std::atoll(e) : (int64_t)-1;
+    }();
+    return chunk < 0 ? -1 : chunk;
+}
 } // namespace
 
 int drm_refs_create(const uint8_t *windows, int64_t n_ref, int32_t ref_len, int64_t row_stride, int device,
@@ -1377,6 +1387,7 @@ int drm_refs_create(const uint8_t *windows, int64_t n_ref, int32_t ref_len, int6
         std::unique_ptr<drm_refs> r(new drm_refs());
         r->dev.device = device;
         r->dev.sw_band = env_sw_band();
+        r->dev.sw_chunk = env_sw_chunk();
         r->dev.n_ref = n_ref;
         r->dev.ref_len = ref_len;
         r->dev.row_stride = std::max<int64_t>(16, ((int64_t)ref_len + 15) / 16 * 16);
@@ -1415,6 +1426,7 @@ int drm_refs_create_genome(const uint8_t *genome, int64_t len, int32_t ref_len, 
         std::unique_ptr<drm_refs> r(new drm_refs());
         r->dev.device = device;
         r->dev.sw_band = env_sw_band();
+        r->dev.sw_chunk = env_sw_chunk();
         r->dev.ref_len = ref_len;
         r->dev.row_stride = 16;
         r->dev.glen = len;
@@ -1468,12 +1480,33 @@ int drm_refs_get_sw_band(const drm_refs *refs, int32_t *band)
     });
 }
 
+int drm_refs_set_sw_chunk(drm_refs *refs, int64_t chunk)
+{
+    return guarded([&] {
+        if (!refs)
+            throw Error(DRM_ERR_ARG, "null argument");
+        if (chunk < -1)
+            throw Error(DRM_ERR_ARG, "SW chunk must be -1 (the library's plan), 0 (one launch) or a number of queries");
+        refs->dev.sw_chunk = chunk;
+    });
+}
+
+int drm_refs_get_sw_chunk(const drm_refs *refs, int64_t *chunk)
+{
+    return guarded([&] {
+        if (!refs || !chunk)
+            throw Error(DRM_ERR_ARG, "null argument");
+        *chunk = refs->dev.sw_chunk;
+    });
+}
+
 int drm_refs_free(drm_refs *refs)
 {
     return guarded([&] {
         if (!refs)
             return;
         (void)hipSetDevice(refs->dev.device);
+        drm::release_sw_rerank(refs->dev);
         for (void *p : {(void *)refs->dev.windows, (void *)refs->dev.ws_ids, (void *)refs->dev.ws_scores,
                         (void *)refs->dev.ws_ncand, (void *)refs->dev.genome, (void *)refs->dev.emb,
                         (void *)refs->dev.ws_qoff, refs->dev.ws_scan})

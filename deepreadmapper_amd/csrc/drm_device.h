@@ -249,6 +249,17 @@ struct DeviceRefs {
     int64_t emb_rows = 0;
     // opt-in banded SW (drm_refs_set_sw_band): 0 = the full DP of the reference (default), else the band half-width
     int32_t sw_band = 0;
+    // SW rerank, pair-profile path (sw_rerank.hip, DESIGN.md sec. 4.4 "Round 8"): queries per chunk of one call
+    // (drm_refs_set_sw_chunk): -1 = the library's plan, 0 = one launch sequence on the caller's stream, n > 0 = chunks of
+    // n queries. The chunks alternate between two streams of the handle's own, made together at the first chunked
+    // call (sw_ev[0]: the caller's stream at entry; sw_ev[1 + i]: the end of stream i) and released with the handle.
+    int64_t sw_chunk = -1;
+    hipStream_t sw_stream[2] = {nullptr, nullptr};
+    hipEvent_t sw_ev[3] = {nullptr, nullptr, nullptr};
+    // the queries a chunk's pair-profile kernel flagged for the bit-profile kernel: one counter per chunk, and the
+    // chunk's list at the chunk's first query in ws_flag_list [ws_nq] (grown with the workspace)
+    uint32_t *ws_flag_count = nullptr, *ws_flag_list = nullptr;
+    size_t ws_flag_chunks = 0, ws_flag_n = 0;
 };
 
 struct RerankArgs {
@@ -275,11 +286,15 @@ struct RerankArgs {
     uint64_t *cand_ids;
     int32_t *cand_scores;
     int32_t *ncand;
+    // pair-profile path: the flagged queries' indices (appended in any order) and their count
+    uint32_t *flag_list, *flag_count;
 };
 
 constexpr int kMaxCands = 1024; // candidates per query kept in LDS
 
 void launch_sw_rerank(DeviceRefs &refs, RerankArgs a, int max_qlen, hipStream_t stream);
+// the handle's rerank streams, events and workspace (drm_refs_free)
+void release_sw_rerank(DeviceRefs &refs);
 
 // generic batched calc_sw_score: one wave per pair
 void launch_sw_pairs(const uint8_t *d_s1, const int64_t *d_off1, const int32_t *d_len1, const uint8_t *d_s2,

@@ -19,6 +19,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <vector>
 
 #include "drm_device.h"
 
@@ -272,9 +273,10 @@ __global__ __launch_bounds__(64) void sw_score_kernel(RerankArgs a)
 
     const int tid = threadIdx.x; // one wave per workgroup
     const int lane = tid & 63;
-    for (int64_t q = blockIdx.x; q < a.nq; q += gridDim.x) {
-        if (ONLY_FLAGGED && a.ncand[q] != -4)
-            continue; // scored by sw_score_f16_kernel
+    // ONLY_FLAGGED: the queries sw_score_f16_kernel listed (in any order: each is re-scored on its own), none as a rule
+    const int64_t nitems = ONLY_FLAGGED ? (int64_t)*a.flag_count : a.nq;
+    for (int64_t it = blockIdx.x; it < nitems; it += gridDim.x) {
+        const int64_t q = ONLY_FLAGGED ? (int64_t)a.flag_list[it] : it;
         const int qlen = a.q_len[q];
         const int nsel = min(a.k_clusters, a.kk);
         const int64_t *nb = a.neighbors + q * a.kk;
@@ -698,8 +700,12 @@ __global__ __launch_bounds__(64) void sw_score_f16_kernel(RerankArgs a)
         if (__ballot(flagged) != 0ull && lane == 0)
             flag_s = 1;
         __syncthreads();
-        if (tid == 0)
-            a.ncand[q] = (ncand >= 0 && flag_s) ? kNeedBitProfile : ncand;
+        if (tid == 0) {
+            const bool rescore = ncand >= 0 && flag_s;
+            a.ncand[q] = rescore ? kNeedBitProfile : ncand;
+            if (rescore) // at most nq entries: every query is listed once
+                a.flag_list[atomicAdd(a.flag_count, 1u)] = (uint32_t)q;
+        }
         __syncthreads();
     }
 }
@@ -1011,6 +1017,146 @@ static int pick_lq(int max_qlen)
                 "query length " + std::to_string(max_qlen) + " > 256 is not supported by the GPU SW kernel yet");
 }
 
+#ifndef DRM_SW_F16_GRID_CAP
+#define DRM_SW_F16_GRID_CAP (1 << 30)
+#endif
+
+// Kernel 2 (sw_topk_kernel) for the a.nq queries of `a`
+static void launch_sw_topk(const RerankArgs &a, hipStream_t stream)
+{
+    // 16-bit elements when every score (<= the window length) and every candidate index fits a byte: half the LDS
+    // per query, twice the queries in flight for the latency-bound heap walk
+    const int64_t cmax = a.cmax;
+    const bool small = a.ref_len <= 255 && cmax <= 256;
+    const size_t esz = small ? 2 : 4;
+    const int stride_words = (int)(((size_t)(cmax + 1) * esz + 3) / 4) | 1; // odd: lanes at one index, distinct banks
+    const int stride = (int)((size_t)stride_words * 4 / esz);
+    int tpb = 64;
+    while (tpb > 1 && (size_t)tpb * (size_t)stride * esz > 65536)
+        tpb >>= 1;
+    const int64_t blocks = (a.nq + tpb - 1) / tpb;
+    if (small)
+        hipLaunchKernelGGL((sw_topk_kernel<uint16_t, 8>), dim3((unsigned)blocks), dim3(tpb), (size_t)tpb * stride * esz,
+                           stream, a, stride);
+    else
+        hipLaunchKernelGGL((sw_topk_kernel<uint32_t, 16>), dim3((unsigned)blocks), dim3(tpb), (size_t)tpb * stride * esz,
+                           stream, a, stride);
+    DRM_HIP_CHECK(hipGetLastError());
+}
+
+// Pair-profile path of the rerank (queries of up to 152 bytes). Per chunk of queries, on one stream: the pair-profile
+// scoring, the bit-profile kernel over the queries that one listed, the top-k. A call of one chunk runs on the
+// caller's stream. A chunked call (DESIGN.md sec. 4.4 "Round 8") puts its chunks alternately on the handle's two
+// streams, so that a chunk's re-scores and its latency-bound top-k (hardly any VALU, one 16.6 KB block beside the
+// scoring's 8 workgroups per CU) run beside the other stream's VALU-bound scoring instead of after the whole call's.
+// The caller's stream keeps its order: both streams start behind an event recorded on it at entry, and it waits for
+// an event from each at exit, so whatever follows on it may reuse the workspace and read the outputs. No host
+// synchronisation.
+constexpr int64_t kSwChunkMinCall = 131072; // the library's plan chunks calls of at least this many queries (at 100,000
+                                            // chunks measured no gain, profiles/r08/rerank_chunk_plans.txt)
+constexpr int64_t kSwMaxChunks = 1024;      // chunks per call at most (a knob below nq / 1024 is raised)
+constexpr int kSwFlaggedGrid = 2048;        // the re-score kernel's fixed grid: 8 one-wave workgroups per CU, its LDS limit
+
+// The chunks' sizes. A knob of n queries: chunks of n. The library's plan: chunks of W = nq / 7.25 (in whole top-k
+// blocks) behind a first one of W / 2, the last one taking what is left (W / 4 to 5 W / 4). The two streams' scoring
+// kernels share the chip evenly, so equal chunks end at the same moment, both streams turn to their top-k and the chip
+// idles as it did after one launch; with the half chunk ahead each stream's top-k falls into the middle of the
+// other's scoring.
+static std::vector<int64_t> sw_chunk_plan(int64_t nq, int64_t knob)
+{
+    std::vector<int64_t> plan;
+    if (knob > 0) {
+        const int64_t per = std::max(knob, (nq + kSwMaxChunks - 1) / kSwMaxChunks);
+        for (int64_t q0 = 0; q0 < nq; q0 += per)
+            plan.push_back(std::min(per, nq - q0));
+    } else if (knob == 0 || nq < kSwChunkMinCall) {
+        plan.push_back(nq);
+    } else {
+        const int64_t W = ((nq * 4 + 28) / 29 + 63) / 64 * 64;
+        plan.push_back((W / 2 + 63) / 64 * 64);
+        int64_t r = nq - plan[0];
+        for (; r > W + W / 4; r -= W)
+            plan.push_back(W);
+        plan.push_back(r);
+    }
+    return plan;
+}
+
+static void launch_sw_pair_profile(DeviceRefs &refs, const RerankArgs &a0, int lq, hipStream_t stream)
+{
+    const int64_t nq = a0.nq;
+    const std::vector<int64_t> plan = sw_chunk_plan(nq, refs.sw_chunk);
+    const size_t nch = plan.size();
+    if (nch > refs.ws_flag_chunks || (size_t)nq > refs.ws_flag_n) {
+        const size_t chunks = std::max(nch, refs.ws_flag_chunks), n = std::max((size_t)nq, refs.ws_flag_n);
+        for (uint32_t **p : {&refs.ws_flag_count, &refs.ws_flag_list})
+            if (*p) {
+                DRM_HIP_CHECK(hipFree(*p)); // waits for the device: no earlier call still uses it
+                *p = nullptr;
+            }
+        refs.ws_flag_chunks = refs.ws_flag_n = 0;
+        DRM_HIP_CHECK(hipMalloc(&refs.ws_flag_count, sizeof(uint32_t) * chunks));
+        DRM_HIP_CHECK(hipMalloc(&refs.ws_flag_list, sizeof(uint32_t) * n));
+        refs.ws_flag_chunks = chunks;
+        refs.ws_flag_n = n;
+    }
+    const bool chunked = nch > 1;
+    if (chunked && !refs.sw_stream[0]) {
+        // made together, so that HIP's round-robin over the hardware queues puts them on different ones (exec.cpp,
+        // ExecCache::init); either may share its queue with the caller's stream, which idles during the call
+        DRM_HIP_CHECK(hipSetDevice(refs.device));
+        for (hipStream_t &s : refs.sw_stream)
+            DRM_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        for (hipEvent_t &ev : refs.sw_ev)
+            DRM_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    }
+    DRM_HIP_CHECK(hipMemsetAsync(refs.ws_flag_count, 0, sizeof(uint32_t) * nch, stream));
+    if (chunked) {
+        DRM_HIP_CHECK(hipEventRecord(refs.sw_ev[0], stream));
+        for (hipStream_t s : refs.sw_stream)
+            DRM_HIP_CHECK(hipStreamWaitEvent(s, refs.sw_ev[0], 0));
+    }
+    const size_t cand_lds = sizeof(uint32_t) * (size_t)a0.cmax; // sw_score_f16_kernel's candidate list
+    int64_t q0 = 0;
+    for (size_t c = 0; c < nch; q0 += plan[c], ++c) {
+        hipStream_t s = chunked ? refs.sw_stream[c & 1] : stream;
+        // the chunk's queries: every per-query array starts at q0 (the workspace rows are per query too)
+        RerankArgs a = a0;
+        a.nq = plan[c];
+        a.neighbors += q0 * a.kk;
+        a.queries += q0 * a.q_stride;
+        a.q_len += q0;
+        a.top_scores += q0 * a.k;
+        a.top_ids += q0 * a.k;
+        a.status += q0;
+        a.cand_ids += q0 * a.cmax;
+        a.cand_scores += q0 * a.cmax;
+        a.ncand += q0;
+        a.flag_list = refs.ws_flag_list + q0;
+        a.flag_count = refs.ws_flag_count + c;
+        // one workgroup per query (a query is ~270k issue cycles of one wave, so the grid's tail is one query, not
+        // the 19-20 a 65536-wave grid-stride hands each wave at C5); the re-scores: a fixed grid over the listed queries
+        const int grid_f16 = (int)std::min<int64_t>(a.nq, (int64_t)DRM_SW_F16_GRID_CAP);
+        const int grid = (int)std::min<int64_t>(a.nq, kSwFlaggedGrid);
+        if (lq == 64) {
+            hipLaunchKernelGGL((sw_score_f16_kernel<64>), dim3(grid_f16), dim3(64), cand_lds, s, a);
+            hipLaunchKernelGGL((sw_score_kernel<64, true>), dim3(grid), dim3(64), 0, s, a);
+        } else {
+            // 150 DP columns: the read's bases; the "<" / ">" tags are dropped in the kernel (a query with more
+            // than 150 columns left after its non-ACGT ends is flagged and scored by the bit-profile kernel)
+            hipLaunchKernelGGL((sw_score_f16_kernel<150>), dim3(grid_f16), dim3(64), cand_lds, s, a);
+            hipLaunchKernelGGL((sw_score_kernel<152, true>), dim3(grid), dim3(64), 0, s, a);
+        }
+        DRM_HIP_CHECK(hipGetLastError());
+        launch_sw_topk(a, s);
+    }
+    if (chunked)
+        for (int i = 0; i < 2; ++i) {
+            DRM_HIP_CHECK(hipEventRecord(refs.sw_ev[1 + i], refs.sw_stream[i]));
+            DRM_HIP_CHECK(hipStreamWaitEvent(stream, refs.sw_ev[1 + i], 0));
+        }
+}
+
 void launch_sw_rerank(DeviceRefs &refs, RerankArgs a, int max_qlen, hipStream_t stream)
 {
     if (a.nq <= 0)
@@ -1042,18 +1188,21 @@ void launch_sw_rerank(DeviceRefs &refs, RerankArgs a, int max_qlen, hipStream_t 
     a.cand_ids = refs.ws_ids;
     a.cand_scores = refs.ws_scores;
     a.ncand = refs.ws_ncand;
-    // the bit-profile kernel: one one-wave workgroup per query up to 65536 (grid-stride beyond)
+    static const bool force_bits = [] {
+        const char *e = std::getenv("DRM_SW_BITPROFILE");
+        return e && std::atoi(e) != 0;
+    }();
+    const int lq = refs.sw_band > 0 ? 0 : pick_lq(max_qlen); // the banded kernel has its own limit (status -3)
+    if (refs.sw_band == 0 && !force_bits && lq <= 152) {
+        // fp16 pair-profile kernel for queries up to 152 bytes; the bit-profile kernel re-scores the queries it flagged
+        launch_sw_pair_profile(refs, a, lq, stream);
+        return;
+    }
+    // the bit-profile kernel: one one-wave workgroup per query up to 65536 (grid-stride beyond); it takes longer
+    // queries (or everything when DRM_SW_BITPROFILE=1)
     const int grid = (int)std::min<int64_t>(a.nq, 65536);
-#ifndef DRM_SW_F16_GRID_CAP
-#define DRM_SW_F16_GRID_CAP (1 << 30)
-#endif
-    // the pair-profile kernel: one workgroup per query (a query is ~270k issue cycles of one wave, so the grid's
-    // tail is one query, not the 19-20 a 65536-wave grid-stride hands each wave at C5)
-    const int grid_f16 = (int)std::min<int64_t>(a.nq, (int64_t)DRM_SW_F16_GRID_CAP);
-    const size_t cand_lds = sizeof(uint32_t) * (size_t)cmax; // sw_score_f16_kernel's candidate list
-    // fp16 pair-profile kernel for queries up to 152 bytes; the bit-profile kernel re-scores the
-    // queries it flagged, and takes longer queries (or everything when DRM_SW_BITPROFILE=1).
     if (refs.sw_band > 0) {
+        const int grid_f16 = (int)std::min<int64_t>(a.nq, (int64_t)DRM_SW_F16_GRID_CAP);
         // opt-in banded DP (non-parity): one kernel for every query (status -3 past its limits)
         const int W = refs.sw_band;
         const int qm = std::max(1, std::min(max_qlen, kBandQMax));
@@ -1072,53 +1221,36 @@ void launch_sw_rerank(DeviceRefs &refs, RerankArgs a, int max_qlen, hipStream_t 
         default:
             throw Error(DRM_ERR_ARG, "SW band must be 8, 16 or 32");
         }
+    } else if (lq == 64) {
+        hipLaunchKernelGGL((sw_score_kernel<64>), dim3(grid), dim3(64), 0, stream, a);
+    } else if (lq == 152) {
+        hipLaunchKernelGGL((sw_score_kernel<152>), dim3(grid), dim3(64), 0, stream, a);
     } else {
-    static const bool force_bits = [] {
-        const char *e = std::getenv("DRM_SW_BITPROFILE");
-        return e && std::atoi(e) != 0;
-    }();
-    switch (pick_lq(max_qlen)) {
-    case 64:
-        if (force_bits) {
-            hipLaunchKernelGGL((sw_score_kernel<64>), dim3(grid), dim3(64), 0, stream, a);
-        } else {
-            hipLaunchKernelGGL((sw_score_f16_kernel<64>), dim3(grid_f16), dim3(64), cand_lds, stream, a);
-            hipLaunchKernelGGL((sw_score_kernel<64, true>), dim3(grid), dim3(64), 0, stream, a);
-        }
-        break;
-    case 152:
-        if (force_bits) {
-            hipLaunchKernelGGL((sw_score_kernel<152>), dim3(grid), dim3(64), 0, stream, a);
-        } else {
-            // 150 DP columns: the read's bases; the "<" / ">" tags are dropped in the kernel (a query with more
-            // than 150 columns left after its non-ACGT ends is flagged and scored by the bit-profile kernel)
-            hipLaunchKernelGGL((sw_score_f16_kernel<150>), dim3(grid_f16), dim3(64), cand_lds, stream, a);
-            hipLaunchKernelGGL((sw_score_kernel<152, true>), dim3(grid), dim3(64), 0, stream, a);
-        }
-        break;
-    default:
         hipLaunchKernelGGL((sw_score_kernel<256>), dim3(grid), dim3(64), 0, stream, a);
-        break;
-    }
     }
     DRM_HIP_CHECK(hipGetLastError());
-    // 16-bit elements when every score (<= the window length) and every candidate index fits a byte: half the LDS
-    // per query, twice the queries in flight for the latency-bound heap walk
-    const bool small = a.ref_len <= 255 && cmax <= 256;
-    const size_t esz = small ? 2 : 4;
-    const int stride_words = (int)(((size_t)(cmax + 1) * esz + 3) / 4) | 1; // odd: lanes at one index, distinct banks
-    const int stride = (int)((size_t)stride_words * 4 / esz);
-    int tpb = 64;
-    while (tpb > 1 && (size_t)tpb * (size_t)stride * esz > 65536)
-        tpb >>= 1;
-    const int64_t blocks = (a.nq + tpb - 1) / tpb;
-    if (small)
-        hipLaunchKernelGGL((sw_topk_kernel<uint16_t, 8>), dim3((unsigned)blocks), dim3(tpb), (size_t)tpb * stride * esz,
-                           stream, a, stride);
-    else
-        hipLaunchKernelGGL((sw_topk_kernel<uint32_t, 16>), dim3((unsigned)blocks), dim3(tpb), (size_t)tpb * stride * esz,
-                           stream, a, stride);
-    DRM_HIP_CHECK(hipGetLastError());
+    launch_sw_topk(a, stream);
+}
+
+void release_sw_rerank(DeviceRefs &refs)
+{
+    for (hipStream_t &s : refs.sw_stream)
+        if (s) {
+            (void)hipStreamSynchronize(s);
+            (void)hipStreamDestroy(s);
+            s = nullptr;
+        }
+    for (hipEvent_t &e : refs.sw_ev)
+        if (e) {
+            (void)hipEventDestroy(e);
+            e = nullptr;
+        }
+    for (uint32_t **p : {&refs.ws_flag_count, &refs.ws_flag_list})
+        if (*p) {
+            (void)hipFree(*p);
+            *p = nullptr;
+        }
+    refs.ws_flag_chunks = refs.ws_flag_n = 0;
 }
 
 void launch_sw_pairs(const uint8_t *d_s1, const int64_t *d_off1, const int32_t *d_len1, const uint8_t *d_s2,

@@ -50,6 +50,18 @@ class _SwBand:
     def sw_band(self, band):
         check(lib().drm_refs_set_sw_band(self._h, int(band)))
 
+    @property
+    def sw_chunk(self):
+        """Queries per chunk of one SW rerank call (drm_refs_set_sw_chunk): -1 = the library's plan, 0 = one launch
+        sequence on the caller's stream; the results are the same bytes in every mode."""
+        n = C.c_int64(0)
+        check(lib().drm_refs_get_sw_chunk(self._h, C.byref(n)))
+        return n.value
+
+    @sw_chunk.setter
+    def sw_chunk(self, chunk):
+        check(lib().drm_refs_set_sw_chunk(self._h, int(chunk)))
+
 
 class WindowTable(_SwBand):
     """Device-resident `ref_seqs` (static lookup table of equal-length windows)."""

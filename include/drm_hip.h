@@ -271,6 +271,14 @@ int drm_refs_get_info(const drm_refs *refs, int64_t *n_ref, int32_t *ref_len, in
  * the rerank fails with DRM_ERR_UNSUPPORTED). */
 int drm_refs_set_sw_band(drm_refs *refs, int32_t band);
 int drm_refs_get_sw_band(const drm_refs *refs, int32_t *band);
+/* How a Smith-Waterman rerank call on this handle splits its queries (results are the same bytes either way; queries
+ * of up to 152 bytes on the full DP only): chunk 0 = one launch sequence on the caller's stream (scoring, re-scores,
+ * top-k); chunk n > 0 = chunks of n queries, alternating between two streams the handle owns, so that a chunk's
+ * top-k runs beside the next chunk's scoring; chunk -1 = the library's plan (chunks for large calls only). The call
+ * stays ordered on the caller's stream in every mode. Below -1: DRM_ERR_ARG. A new handle starts at $DRM_SW_CHUNK
+ * (read once per process; unset: -1). */
+int drm_refs_set_sw_chunk(drm_refs *refs, int64_t chunk);
+int drm_refs_get_sw_chunk(const drm_refs *refs, int64_t *chunk);
 
 /* post_process_sw_static (src/utils/post_processor.cpp:454-549) -> find_sequences (static,
  * :204-336) -> sw_reranker (src/utils/reranker.cpp:3-51) -> calc_sw_score, for nq queries.
