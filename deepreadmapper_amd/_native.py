@@ -54,6 +54,8 @@ EXPORTS = [
     "drm_hit_mapq", "drm_hit_mapq_device", "drm_pair_mapq", "drm_pair_mapq_device", "drm_mapq_value",
     "drm_pair_mapq_rescued",
     "drm_tlen_scan", "drm_tlen_scan_device", "drm_tlen_estimate",
+    "drm_fasta_contigs", "drm_contigs_create", "drm_contigs_free", "drm_contigs_find", "drm_contig_lds_max",
+    "drm_contig_hits", "drm_contig_hits_device",
 ]
 
 
@@ -228,6 +230,13 @@ def lib():
         "drm_tlen_scan": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i64, vp, vp]),
         "drm_tlen_scan_device": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i64, vp, vp, vp]),
         "drm_tlen_estimate": (C.c_int, [vp, i32, i32, vp]),
+        "drm_fasta_contigs": (C.c_int, [C.c_char_p, C.POINTER(i64), vp, vp, vp, C.POINTER(i64)]),
+        "drm_contigs_create": (C.c_int, [vp, vp, i64, C.c_int, C.POINTER(vp)]),
+        "drm_contigs_free": (C.c_int, [vp]),
+        "drm_contigs_find": (C.c_int, [vp, i64, i64, C.POINTER(i32)]),
+        "drm_contig_lds_max": (C.c_int, []),
+        "drm_contig_hits": (C.c_int, [vp, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp]),
+        "drm_contig_hits_device": (C.c_int, [vp, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp]),
         "drm_exact_search": (C.c_int, [vp, vp, i64, i32, i32, vp, vp, C.POINTER(C.c_double)]),
         "drm_exact_search_device": (C.c_int, [vp, vp, i64, i32, vp, vp, vp]),
         "drm_exact_search_l2": (C.c_int, [vp, i64, i32, vp, i64, i32, vp, vp, C.POINTER(C.c_double)]),

@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <mutex>
 #include <numeric>
 #include <thread>
 #include <unordered_set>
@@ -2214,6 +2215,203 @@ int drm_mate_rescue(drm_refs *refs, const drm_sw_scoring *scoring, const drm_pai
         drm::launch_mate_rescue(refs->dev.device, a, in.longest, nullptr);
         DRM_HIP_CHECK(hipDeviceSynchronize());
         dout.download(out);
+    });
+}
+
+// ---------------------------------------------------------------------- contig stage (contig_hits.hip)
+struct drm_contigs {
+    std::vector<int64_t> starts, ends; // contig t is [starts[t], ends[t]) of the genome string
+    int device = 0;
+    // the device copy, made by the first drm_contig_hits[_device]: the table and its host lookup need no device
+    mutable std::mutex upload_lock;
+    mutable uint64_t *d_starts = nullptr, *d_ends = nullptr;
+};
+
+static void contigs_upload(const drm_contigs *c)
+{
+    std::lock_guard<std::mutex> hold(c->upload_lock);
+    DRM_HIP_CHECK(hipSetDevice(c->device));
+    if (c->d_starts)
+        return;
+    DevBuf<uint64_t> ds(c->starts.size()), de(c->ends.size());
+    ds.upload(reinterpret_cast<const uint64_t *>(c->starts.data()));
+    de.upload(reinterpret_cast<const uint64_t *>(c->ends.data()));
+    c->d_starts = ds.p;
+    c->d_ends = de.p;
+    ds.p = de.p = nullptr;
+}
+
+int drm_contigs_create(const int64_t *starts, const int64_t *lens, int64_t n, int device, drm_contigs **out)
+{
+    return guarded([&] {
+        if (!starts || !lens || !out)
+            throw Error(DRM_ERR_ARG, "null argument");
+        if (device < 0)
+            throw Error(DRM_ERR_ARG, "negative device");
+        if (n < 1 || n > ((int64_t)1 << 20))
+            throw Error(DRM_ERR_ARG, std::to_string(n) + " contigs, outside [1, 2^20]");
+        int64_t prev_end = 0;
+        for (int64_t t = 0; t < n; ++t) {
+            if (starts[t] < prev_end || lens[t] < 1 || lens[t] > ((int64_t)1 << 40) ||
+                starts[t] > ((int64_t)1 << 40) - lens[t])
+                throw Error(DRM_ERR_ARG, "contig " + std::to_string(t) + ": start " + std::to_string(starts[t]) +
+                                             ", length " + std::to_string(lens[t]) +
+                                             ": the table must be ascending and disjoint, lengths >= 1, ends <= 2^40");
+            prev_end = starts[t] + lens[t];
+        }
+        std::unique_ptr<drm_contigs> c(new drm_contigs);
+        c->device = device;
+        c->starts.assign(starts, starts + n);
+        c->ends.resize((size_t)n);
+        for (int64_t t = 0; t < n; ++t)
+            c->ends[(size_t)t] = starts[t] + lens[t];
+        // where the device is there, the copy is made now (the caller's current device is put back); without one the
+        // table still serves drm_contigs_find, and the first stage call makes the copy
+        int ndev = 0, cur = 0;
+        if (hipGetDeviceCount(&ndev) == hipSuccess && device < ndev && hipGetDevice(&cur) == hipSuccess) {
+            contigs_upload(c.get());
+            DRM_HIP_CHECK(hipSetDevice(cur));
+        } else {
+            (void)hipGetLastError(); // no device: not this call's error
+        }
+        *out = c.release();
+    });
+}
+
+int drm_contigs_free(drm_contigs *c)
+{
+    return guarded([&] {
+        if (!c)
+            return;
+        if (c->d_starts) {
+            (void)hipSetDevice(c->device);
+            (void)hipFree(c->d_starts);
+            (void)hipFree(c->d_ends);
+        }
+        delete c;
+    });
+}
+
+int drm_contigs_find(const drm_contigs *c, int64_t pos, int64_t span, int32_t *contig)
+{
+    return guarded([&] {
+        if (!c || !contig)
+            throw Error(DRM_ERR_ARG, "null argument");
+        *contig = -1;
+        if (pos < 0 || span < 0 || pos > INT64_MAX - span)
+            return;
+        const auto it = std::upper_bound(c->starts.begin(), c->starts.end(), pos); // the first start > pos
+        if (it == c->starts.begin())
+            return;
+        const size_t t = (size_t)(it - c->starts.begin()) - 1;
+        if (pos + span <= c->ends[t])
+            *contig = (int32_t)t;
+    });
+}
+
+int drm_contig_lds_max(void) { return drm::kContigLdsMax; }
+
+static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return na && nb && x < y + nb && y < x + na;
+}
+
+static drm::ContigArgs make_contig_args(const drm_contigs *c, int32_t ref_len, const uint64_t *ids,
+                                        const int32_t *scores, const int32_t *cnt, int64_t nreads, int32_t k,
+                                        uint64_t *out_ids, uint64_t *out_spread, int32_t *out_scores,
+                                        int32_t *out_contig, int32_t *out_cnt)
+{
+    if (!c)
+        throw Error(DRM_ERR_ARG, "null contig table");
+    if (k < 0 || k > drm::kMaxCands)
+        throw Error(DRM_ERR_UNSUPPORTED, "k = " + std::to_string(k) + " outside [0, 1024], the rerank's candidate cap");
+    if (ref_len < 1 || ref_len > (1 << 20))
+        throw Error(DRM_ERR_ARG, "ref_len " + std::to_string(ref_len) + " outside [1, 2^20]");
+    if (nreads < 0)
+        throw Error(DRM_ERR_ARG, "nreads must be >= 0");
+    if (nreads > 0 && (!cnt || !out_cnt ||
+                       (k > 0 && (!ids || !scores || !out_ids || !out_spread || !out_scores || !out_contig))))
+        throw Error(DRM_ERR_ARG, "null argument");
+    const size_t rows = (size_t)nreads * (size_t)k;
+    const struct {
+        const void *p;
+        size_t bytes;
+    } in[3] = {{ids, 8 * rows}, {scores, 4 * rows}, {cnt, 4 * (size_t)nreads}},
+      o[5] = {{out_ids, 8 * rows}, {out_spread, 8 * rows}, {out_scores, 4 * rows}, {out_contig, 4 * rows},
+              {out_cnt, 4 * (size_t)nreads}};
+    for (int x = 0; x < 5; ++x) {
+        for (int y = 0; y < 3; ++y)
+            if (ranges_overlap(o[x].p, o[x].bytes, in[y].p, in[y].bytes))
+                throw Error(DRM_ERR_ARG, "an output overlaps an input: the contig stage does not run in place");
+        for (int y = x + 1; y < 5; ++y)
+            if (ranges_overlap(o[x].p, o[x].bytes, o[y].p, o[y].bytes))
+                throw Error(DRM_ERR_ARG, "two outputs overlap");
+    }
+    drm::ContigArgs a{}; // starts / ends: contigs_upload, once there is something to run
+    a.n = (int32_t)c->starts.size();
+    a.ref_len = ref_len;
+    a.ids = ids;
+    a.scores = scores;
+    a.cnt = cnt;
+    a.nreads = nreads;
+    a.k = k;
+    a.out_ids = out_ids;
+    a.out_spread = out_spread;
+    a.out_scores = out_scores;
+    a.out_contig = out_contig;
+    a.out_cnt = out_cnt;
+    return a;
+}
+
+int drm_contig_hits_device(const drm_contigs *c, int32_t ref_len, const uint64_t *d_ids, const int32_t *d_scores,
+                           const int32_t *d_cnt, int64_t nreads, int32_t k, uint64_t *d_out_ids,
+                           uint64_t *d_out_spread, int32_t *d_out_scores, int32_t *d_out_contig, int32_t *d_out_cnt,
+                           void *stream)
+{
+    return guarded([&] {
+        drm::ContigArgs a = make_contig_args(c, ref_len, d_ids, d_scores, d_cnt, nreads, k, d_out_ids, d_out_spread,
+                                             d_out_scores, d_out_contig, d_out_cnt);
+        if (nreads == 0)
+            return;
+        contigs_upload(c);
+        a.starts = c->d_starts;
+        a.ends = c->d_ends;
+        drm::launch_contig_hits(a, (hipStream_t)stream);
+    });
+}
+
+int drm_contig_hits(const drm_contigs *c, int32_t ref_len, const uint64_t *ids, const int32_t *scores,
+                    const int32_t *cnt, int64_t nreads, int32_t k, uint64_t *out_ids, uint64_t *out_spread,
+                    int32_t *out_scores, int32_t *out_contig, int32_t *out_cnt)
+{
+    return guarded([&] {
+        drm::ContigArgs a = make_contig_args(c, ref_len, ids, scores, cnt, nreads, k, out_ids, out_spread, out_scores,
+                                             out_contig, out_cnt);
+        if (nreads == 0)
+            return;
+        contigs_upload(c);
+        a.starts = c->d_starts;
+        a.ends = c->d_ends;
+        const size_t rows = (size_t)nreads * (size_t)k;
+        const HitLists d(ids, scores, cnt, nullptr, (size_t)nreads, k);
+        DevBuf<uint64_t> doi(rows), dos(rows);
+        DevBuf<int32_t> dosc(rows), doc(rows), dcnt((size_t)nreads);
+        d.bind(a.ids, a.scores, a.cnt);
+        a.out_ids = doi.p;
+        a.out_spread = dos.p;
+        a.out_scores = dosc.p;
+        a.out_contig = doc.p;
+        a.out_cnt = dcnt.p;
+        drm::launch_contig_hits(a, nullptr);
+        DRM_HIP_CHECK(hipDeviceSynchronize());
+        if (k > 0) {
+            doi.download(out_ids);
+            dos.download(out_spread);
+            dosc.download(out_scores);
+            doc.download(out_contig);
+        }
+        dcnt.download(out_cnt);
     });
 }
 

@@ -413,6 +413,26 @@ struct TlenArgs {
 };
 void launch_tlen_scan(const TlenArgs &a, hipStream_t stream);
 
+// Contig stage (contig_hits.hip; drm_contig_hits): one wave per read, the rows whose window lies
+// inside one contig compacted stably, with their spread ids. Runs on the current device and throws
+// Error(DRM_ERR_UNSUPPORTED) for k outside [0, kMaxCands].
+constexpr int kContigLdsMax = 1024; // contigs searched in LDS (16 KB of starts and ends); beyond: global memory
+struct ContigArgs {
+    const uint64_t *starts, *ends; // [n] on the device: contig t is [starts[t], ends[t])
+    int32_t n;                     // 1 .. 2^20
+    int32_t ref_len;
+    const uint64_t *ids;   // [nreads][k]
+    const int32_t *scores; // [nreads][k]
+    const int32_t *cnt;    // [nreads]
+    int64_t nreads;
+    int32_t k;
+    uint64_t *out_ids, *out_spread;  // [nreads][k]
+    int32_t *out_scores, *out_contig; // [nreads][k]
+    int32_t *out_cnt;                 // [nreads]
+    int32_t steps; // set by the launch: ceil(log2 n), the trips of the binary search
+};
+void launch_contig_hits(ContigArgs a, hipStream_t stream);
+
 // L2 rerank (post_process_l2_static -> batch_reranker, src/utils/post_processor.cpp:1023-1162,
 // src/utils/reranker.cpp:98-195): distances from the window embedding table, libstdc++ partial_sort
 struct L2Args {

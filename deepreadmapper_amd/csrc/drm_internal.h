@@ -136,6 +136,13 @@ std::string read_whole_file(const std::string &path);
 // extract_FASTA_sequence (parse_inputs.cpp:174-220): skip the first line, keep the upper-cased
 // A/C/G/T/N letters of everything after it (later header lines included), drop the rest.
 std::string extract_fasta_sequence(const std::string &path);
+// The contigs of a FASTA in the coordinates of extract_fasta_sequence's string (include/drm_hip.h,
+// drm_fasta_contigs); throws Error(DRM_ERR_FORMAT) naming the contig.
+struct FastaContig {
+    std::string name;
+    int64_t start = 0, len = 0;
+};
+std::vector<FastaContig> fasta_contigs(const std::string &path);
 // write_sam / write_sam_streaming (utils.cpp:336-503) for one block of queries: the SAM lines of
 // queries [q0, q0 + nq) whose ids[i][0 .. counts[i]) are dense window ids (ids[i] at ids + i * k).
 // `header` writes @HD / @SQ first (SN ref_name, LN ref_len: the reference's quirk) and truncates.
@@ -155,12 +162,22 @@ struct SamAlignments {
     const int64_t *region_start = nullptr;
     const int32_t *region_len = nullptr;
 };
+// `ctg` (DRM_CONTIGS, with `aln` only; null = the one sequence ref_name): the contig table of the reference and the
+// contig of every row, indexed like ids. The header then holds one @SQ line per contig in file order (SN its name, LN
+// its length), a row's RNAME is its contig's name and its POS counts from the contig's start; write_sam_block writes a
+// query without rows as one unmapped line (flag 4). In write_sam_pairs an unmapped mate takes its mate's RNAME and POS;
+// mates on one contig print RNEXT "=", mates on two the other's name and local PNEXT, TLEN 0 and never flag 0x2.
+struct SamContigs {
+    const std::vector<FastaContig> *table;
+    const int32_t *row_contig;
+};
 // `mapq` (DRM_SAM_MAPQ, null = "60" on every line): the MAPQ column of the block's rows, mapq[i * k + j] for row j of
 // query i; a row written unmapped prints 0.
 void write_sam_block(const std::string &path, bool header, const std::string &ref_name, size_t ref_len,
                      const std::vector<std::string> &query_seqs, const std::vector<std::string> &query_ids,
                      size_t q0, size_t nq, const uint64_t *ids, const int32_t *counts, size_t k,
-                     const SamAlignments *aln = nullptr, const int32_t *mapq = nullptr);
+                     const SamAlignments *aln = nullptr, const int32_t *mapq = nullptr,
+                     const SamContigs *ctg = nullptr);
 // The paired form (DRM_MATES, no reference counterpart): the two primary lines of pairs whose reads are queries
 // q0 + 2 * p (mate 1) and q0 + 2 * p + 1 (mate 2). Row r = 2 * p + m of the block carries the read's chosen window
 // ids[r] (counts[r] = 1, or 0 for a read without a hit) and its alignment aln.rec[r] as in the DRM_SAM_CIGAR mode
@@ -172,7 +189,7 @@ void write_sam_block(const std::string &path, bool header, const std::string &re
 void write_sam_pairs(const std::string &path, bool header, const std::string &ref_name, size_t ref_len,
                      const std::vector<std::string> &query_seqs, const std::vector<std::string> &query_ids,
                      size_t q0, size_t npairs, const uint64_t *ids, const int32_t *counts, const int32_t *proper,
-                     const SamAlignments &aln, const int32_t *mapq = nullptr);
+                     const SamAlignments &aln, const int32_t *mapq = nullptr, const SamContigs *ctg = nullptr);
 
 // Mate rescue (include/drm_hip.h, drm_mate_rescue): the region of one anchor id, the one statement of the rule that
 // the host entry points (formats.cpp) and the kernel (mate_rescue.hip) both compile. dlo / dhi are

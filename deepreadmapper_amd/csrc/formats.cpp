@@ -11,6 +11,7 @@
 #include <filesystem>
 #include <fstream>
 #include <sstream>
+#include <unordered_set>
 
 #include "drm_internal.h"
 
@@ -330,6 +331,104 @@ std::string drm::extract_fasta_sequence(const std::string &path)
     return g;
 }
 
+// ----------------------------------------------------------------------- contig table of a FASTA
+std::vector<drm::FastaContig> drm::fasta_contigs(const std::string &path)
+{
+    const std::string data = read_whole_file(path);
+    std::vector<FastaContig> out;
+    std::unordered_set<std::string> seen;
+    int64_t glen = 0; // the length of extract_fasta_sequence's string so far
+    auto label = [&]() {
+        return "contig " + std::to_string(out.size() - 1) + " (\"" + out.back().name + "\")";
+    };
+    auto close = [&]() { // the open contig ends at glen
+        out.back().len = glen - out.back().start;
+        if (out.back().len == 0)
+            throw Error(DRM_ERR_FORMAT, path + ": " + label() + " has no sequence");
+    };
+    auto is_base = [](unsigned char c) {
+        const int u = std::toupper(c);
+        return u == 'A' || u == 'T' || u == 'C' || u == 'G' || u == 'N';
+    };
+    if (data.empty() || data[0] != '>')
+        throw Error(DRM_ERR_FORMAT, path + ": the first line does not start with '>' (the header of contig 0)");
+    for (size_t p = 0; p < data.size();) {
+        size_t e = data.find('\n', p);
+        e = e == std::string::npos ? data.size() : e;
+        if (data[p] == '>') {
+            if (!out.empty()) {
+                close();
+                for (size_t i = p; i < e; ++i) // a later header's letters are a gap in the string
+                    glen += is_base((unsigned char)data[i]);
+            }
+            size_t q = p + 1;
+            while (q < e && !std::isspace((unsigned char)data[q]))
+                ++q;
+            FastaContig c;
+            c.name = data.substr(p + 1, q - p - 1);
+            c.start = glen;
+            if (c.name.empty())
+                throw Error(DRM_ERR_FORMAT, path + ": contig " + std::to_string(out.size()) + " has an empty name");
+            if (!seen.insert(c.name).second)
+                throw Error(DRM_ERR_FORMAT, path + ": contig " + std::to_string(out.size()) + " repeats the name \"" +
+                                                c.name + "\"");
+            out.push_back(std::move(c));
+        } else {
+            for (size_t i = p; i < e; ++i) {
+                const unsigned char c = (unsigned char)data[i];
+                if (std::isspace(c))
+                    continue;
+                if (!is_base(c))
+                    throw Error(DRM_ERR_FORMAT, path + ": " + label() + " holds the byte '" + std::string(1, (char)c) +
+                                                    "' at base " + std::to_string(glen - out.back().start) +
+                                                    ": only A, C, G, T and N are kept, so it would shift every later "
+                                                    "coordinate");
+                ++glen;
+            }
+        }
+        p = e + 1;
+    }
+    close();
+    return out;
+}
+
+extern "C" int drm_fasta_contigs(const char *path, int64_t *n, int64_t *starts, int64_t *lens, char *names,
+                                 int64_t *names_bytes)
+{
+    try {
+        if (!path || !n || !names_bytes)
+            throw drm::Error(DRM_ERR_ARG, "null argument");
+        const std::vector<drm::FastaContig> t = drm::fasta_contigs(path);
+        int64_t bytes = 0;
+        for (const drm::FastaContig &c : t)
+            bytes += (int64_t)c.name.size() + 1;
+        if (starts) {
+            if (*n < (int64_t)t.size() || (names && *names_bytes < bytes))
+                throw drm::Error(DRM_ERR_ARG, "the arrays are too small for " + std::to_string(t.size()) +
+                                                  " contigs and " + std::to_string(bytes) + " bytes of names");
+            char *w = names;
+            for (size_t i = 0; i < t.size(); ++i) {
+                starts[i] = t[i].start;
+                if (lens)
+                    lens[i] = t[i].len;
+                if (names) {
+                    std::memcpy(w, t[i].name.c_str(), t[i].name.size() + 1);
+                    w += t[i].name.size() + 1;
+                }
+            }
+        }
+        *n = (int64_t)t.size();
+        *names_bytes = bytes;
+        return DRM_OK;
+    } catch (const drm::Error &e) {
+        drm::set_last_error(e.what());
+        return e.code;
+    } catch (const std::exception &e) {
+        drm::set_last_error(e.what());
+        return DRM_ERR_IO;
+    }
+}
+
 // ----------------------------------------------------------------------- SAM from a GPU alignment
 // CIGAR + POS of one drm_sw_alignment record over the region genome[region_start ..+ region_len), reverse-complemented
 // when rev (include/drm_hip.h: drm_sam_cigar_region; drm_sam_cigar is the region of a window id)
@@ -402,7 +501,7 @@ extern "C" int drm_sam_cigar(const drm_sw_alignment *a, const uint32_t *ops, int
 // alignment is written as unmapped
 static void append_aligned_row(std::string &buf, const std::string &qname, int flag, const std::string &ref_name,
                                size_t ref_len, const std::string &tagged, uint64_t sid,
-                               const drm::SamAlignments &aln, size_t row, const int32_t *mapq)
+                               const drm::SamAlignments &aln, size_t row, const int32_t *mapq, int64_t contig_start = 0)
 {
     const drm_sw_alignment &a = aln.rec[row];
     // the read is the query without format_fastq's tags (an untagged .txt query is the read itself)
@@ -424,7 +523,7 @@ static void append_aligned_row(std::string &buf, const std::string &qname, int f
     buf += '\t';
     buf += ref_name;
     buf += '\t';
-    buf += std::to_string(pos1);
+    buf += std::to_string(a.status == 1 ? pos1 : pos1 - contig_start); // DRM_CONTIGS: the contig's own coordinate
     buf += '\t';
     buf += mapq ? std::to_string(a.status == 1 ? 0 : mapq[row]) : std::string("60");
     buf += '\t';
@@ -439,19 +538,31 @@ static void append_aligned_row(std::string &buf, const std::string &qname, int f
     buf += '\n';
 }
 
+// @HD, then @SQ: the reference's one line, or with a contig table (DRM_CONTIGS) one line per contig in file order
+static void sam_header(std::ofstream &out, const std::string &ref_name, size_t ref_len, const drm::SamContigs *ctg)
+{
+    out << "@HD\tVN:1.0\tSO:unsorted\n";
+    if (!ctg) {
+        out << "@SQ\tSN:" << ref_name << "\tLN:" << ref_len << "\n";
+        return;
+    }
+    for (const drm::FastaContig &c : *ctg->table)
+        out << "@SQ\tSN:" << c.name << "\tLN:" << c.len << "\n";
+}
+
 // ----------------------------------------------------------------------- SAM (write_sam)
 void drm::write_sam_block(const std::string &path, bool header, const std::string &ref_name, size_t ref_len,
                           const std::vector<std::string> &query_seqs, const std::vector<std::string> &query_ids,
                           size_t q0, size_t nq, const uint64_t *ids, const int32_t *counts, size_t k,
-                          const SamAlignments *aln, const int32_t *mapq)
+                          const SamAlignments *aln, const int32_t *mapq, const SamContigs *ctg)
 {
+    if (ctg && !aln)
+        throw Error(DRM_ERR_ARG, "a contig table needs the rows' alignments");
     std::ofstream out(path, header ? std::ios::out : std::ios::app);
     if (!out.is_open())
         throw Error(DRM_ERR_IO, "Failed to open SAM file: " + path);
-    if (header) {
-        out << "@HD\tVN:1.0\tSO:unsorted\n";
-        out << "@SQ\tSN:" << ref_name << "\tLN:" << ref_len << "\n";
-    }
+    if (header)
+        sam_header(out, ref_name, ref_len, ctg);
     std::string buf;
     for (size_t i = 0; i < nq; ++i) {
         const size_t g = q0 + i;
@@ -466,6 +577,12 @@ void drm::write_sam_block(const std::string &path, bool header, const std::strin
             int flag = j == 0 ? 0 : 256; // primary / secondary
             if (sid % 2 == 1)
                 flag |= 16; // reverse complement
+            if (ctg) {
+                const FastaContig &c = (*ctg->table)[(size_t)ctg->row_contig[i * k + (size_t)j]];
+                append_aligned_row(buf, qname, flag, c.name, ref_len, query_seqs[g], sid, *aln, i * k + (size_t)j, mapq,
+                                   c.start);
+                continue;
+            }
             if (aln) {
                 append_aligned_row(buf, qname, flag, ref_name, ref_len, query_seqs[g], sid, *aln, i * k + (size_t)j,
                                    mapq);
@@ -486,6 +603,8 @@ void drm::write_sam_block(const std::string &path, bool header, const std::strin
             buf += clean;
             buf += "\t*\n";
         }
+        if (ctg && counts[i] < 1) // DRM_CONTIGS: a read without a row inside a contig is written unmapped
+            buf += qname + "\t4\t*\t0\t0\t*\t*\t0\t0\t" + (clean.empty() ? std::string("*") : clean) + "\t*\n";
         if (buf.size() > (1u << 22)) {
             out << buf;
             buf.clear();
@@ -868,15 +987,13 @@ extern "C" int drm_tlen_estimate(const uint32_t *hist_row, int32_t nbins, int32_
 void drm::write_sam_pairs(const std::string &path, bool header, const std::string &ref_name, size_t ref_len,
                           const std::vector<std::string> &query_seqs, const std::vector<std::string> &query_ids,
                           size_t q0, size_t npairs, const uint64_t *ids, const int32_t *counts, const int32_t *proper,
-                          const SamAlignments &aln, const int32_t *mapq)
+                          const SamAlignments &aln, const int32_t *mapq, const SamContigs *ctg)
 {
     std::ofstream out(path, header ? std::ios::out : std::ios::app);
     if (!out.is_open())
         throw Error(DRM_ERR_IO, "Failed to open SAM file: " + path);
-    if (header) {
-        out << "@HD\tVN:1.0\tSO:unsorted\n";
-        out << "@SQ\tSN:" << ref_name << "\tLN:" << ref_len << "\n";
-    }
+    if (header)
+        sam_header(out, ref_name, ref_len, ctg);
     std::string buf;
     for (size_t p = 0; p < npairs; ++p) {
         drm_sam_mate in[2];
@@ -900,9 +1017,25 @@ void drm::write_sam_pairs(const std::string &path, bool header, const std::strin
             else
                 sam_cigar(a, aln.ops + aln.ops_off[row], (int32_t)tagged.size(), pre, post, (int64_t)(sid / 2),
                           (int32_t)ref_len, (sid & 1u) != 0, pos1, cigar[m]);
+            if (ctg) // DRM_CONTIGS: the contig's own coordinate
+                pos1 -= (*ctg->table)[(size_t)ctg->row_contig[row]].start;
             in[m] = drm_sam_mate{1, (int32_t)(sid & 1u), pos1, a.ref_end - a.ref_begin};
         }
-        sam_pair_fields(in, proper[p] != 0, f);
+        // DRM_CONTIGS: RNAME is the contig of the line's own position (an unmapped mate takes its mate's), RNEXT "=" on
+        // one contig; mates on two contigs are never a proper pair and have no template length
+        const std::string *rname[2] = {&ref_name, &ref_name};
+        bool split = false;
+        if (ctg) {
+            for (int m = 0; m < 2; ++m) {
+                const int src = in[m].mapped ? m : 1 - m;
+                if (in[src].mapped)
+                    rname[m] = &(*ctg->table)[(size_t)ctg->row_contig[2 * p + (size_t)src]].name;
+            }
+            split = in[0].mapped && in[1].mapped && ctg->row_contig[2 * p] != ctg->row_contig[2 * p + 1];
+        }
+        sam_pair_fields(in, proper[p] != 0 && !split, f);
+        if (split)
+            f[0].tlen = f[1].tlen = 0;
         const size_t g = q0 + 2 * p;
         const std::string qname = (g < query_ids.size() && !query_ids[g].empty()) ? query_ids[g]
                                                                                   : "S1/" + std::to_string(g / 2 + 1) + "/0";
@@ -911,14 +1044,14 @@ void drm::write_sam_pairs(const std::string &path, bool header, const std::strin
             buf += '\t';
             buf += std::to_string(f[m].flag);
             buf += '\t';
-            buf += f[m].has_rname ? ref_name : std::string("*");
+            buf += f[m].has_rname ? *rname[m] : std::string("*");
             buf += '\t';
             buf += std::to_string(f[m].pos);
             buf += '\t';
             buf += mapq ? std::to_string(in[m].mapped ? mapq[2 * p + (size_t)m] : 0) : std::string("60");
             buf += '\t';
             buf += in[m].mapped ? cigar[m] : std::string("*");
-            buf += f[m].has_rname ? "\t=\t" : "\t*\t";
+            buf += !f[m].has_rname ? "\t*\t" : split ? "\t" + *rname[1 - m] + "\t" : std::string("\t=\t");
             buf += std::to_string(f[m].pnext);
             buf += '\t';
             buf += std::to_string(f[m].tlen);

@@ -685,6 +685,64 @@ typedef struct {
 } drm_tlen_estimate_t;
 int drm_tlen_estimate(const uint32_t *hist_row, int32_t nbins, int32_t min_samples, drm_tlen_estimate_t *out);
 
+/* ---------------------------------------------------------------- Multi-contig references
+ * A FASTA of several sequences is mapped through the one string g that drm_extract_fasta_sequence returns for it, and a
+ * contig table says which stretches of g are contigs. The reference treats every FASTA as one sequence, so this text is
+ * the definition.
+ * Contig table of a FASTA. Lines end at '\n'. The first line must start with '>': it is contig 0's header and adds
+ * nothing to g. Every later line whose first byte is '>' is a header too; its A/C/G/T/N letters (either case) are part
+ * of g, as drm_extract_fasta_sequence keeps them, and form a gap that belongs to no contig: the next contig starts at
+ * the length of g after them. A contig's len is the number of letters appended to g from its header to the next header
+ * or the end of the file; its name is the header after '>', up to the first white-space byte. So
+ * g[start, start + len) is exactly the contig's sequence, and the table is ascending and disjoint.
+ * DRM_ERR_FORMAT, the message naming the contig by index and name: a first line without '>', an empty or a duplicate
+ * name, a contig of length 0, and a sequence line holding a non-space byte that drm_extract_fasta_sequence drops
+ * (IUPAC R or Y, say: it would shift every later coordinate against the FASTA's own).
+ * Two calls: with starts == NULL, *n receives the number of contigs and *names_bytes the size of the names, each
+ * followed by a NUL; then, with *n and *names_bytes the capacities (DRM_ERR_ARG when too small), starts[*n], lens[*n]
+ * and names[*names_bytes] are filled (lens and names may be NULL). */
+int drm_fasta_contigs(const char *path, int64_t *n, int64_t *starts, int64_t *lens, char *names, int64_t *names_bytes);
+/* A contig table for `device`: 1 <= n <= 2^20 contigs, starts ascending, lens >= 1, start + len <= the next start and
+ * <= 2^40 (DRM_ERR_ARG otherwise). Host pointers. Where `device` exists the table is copied to it here, synchronously,
+ * and the caller's current device is left as it was. Without a device the handle still serves drm_contigs_find, and
+ * the copy is made by the first drm_contig_hits[_device] that has reads to process: that one call then allocates and
+ * copies synchronously before it enqueues, so it must not run inside a stream capture. */
+typedef struct drm_contigs drm_contigs;
+int drm_contigs_create(const int64_t *starts, const int64_t *lens, int64_t n, int device, drm_contigs **out);
+int drm_contigs_free(drm_contigs *c);
+/* Host only: *contig = the contig t with start_t <= pos and pos + span <= start_t + len_t, or -1 (pos < 0, span < 0
+ * or a sum beyond int64: -1). Of two adjoining contigs an empty span at their seam belongs to the later one: t is the
+ * last contig that starts at or before pos, as in the contig stage. */
+int drm_contigs_find(const drm_contigs *c, int64_t pos, int64_t span, int32_t *contig);
+/* The largest table the contig stage searches in LDS; a larger one is searched in global memory (L2). */
+int drm_contig_lds_max(void);
+/* The contig stage: the step between the rerank and everything that consumes its rows. ids / scores [nreads x k] and
+ * cnt[nreads] are a rerank's outputs, a count outside [0, k] being clamped as everywhere. For read r, over its counted
+ * rows in order, with p = id >> 1 compared in unsigned 64-bit arithmetic: a row is kept iff some contig t has
+ * start_t <= p and p + ref_len <= start_t + len_t, i.e. its window lies wholly inside one contig. The score does not
+ * decide: a dead row (score 0) inside a contig stays. The kept rows are written in their original order to rows
+ * 0 .. m - 1 of out_ids = id, out_spread = id + (t << 33), out_scores = score, out_contig = t, and out_cnt[r] = m;
+ * rows m .. k - 1 get ids and spread ids 2^64 - 1, score 0 and contig -1.
+ * A spread id is the position shifted by t * 2^32. drm_pair_hits, drm_hit_mapq, drm_pair_mapq and drm_tlen_scan accept
+ * any u64 id and their distances (max_tlen <= 2^30, locus_span <= 2^20, max_scan <= 2^16) are below 2^32, while the
+ * table is ascending, so that two rows of different contigs lie at least 2^32 apart: fed spread ids they never pair,
+ * merge or measure across a contig boundary, and inside one contig they see the differences they see with the real
+ * ids. Spread positions stay below 2^20 * 2^32 + 2^40 < 2^63.
+ * Arguments: 0 <= k <= 1024 (beyond: DRM_ERR_UNSUPPORTED), 1 <= ref_len <= 2^20, nreads >= 0, no null pointer, and
+ * no output overlapping an input or another output (DRM_ERR_ARG otherwise). Runs on the table's device.
+ * Host pointers; out arrays [nreads x k], out_cnt[nreads]. */
+int drm_contig_hits(const drm_contigs *c, int32_t ref_len, const uint64_t *ids, const int32_t *scores,
+                    const int32_t *cnt, int64_t nreads, int32_t k, uint64_t *out_ids, uint64_t *out_spread,
+                    int32_t *out_scores, int32_t *out_contig, int32_t *out_cnt);
+/* Device-buffer form, enqueued on `stream`. It consumes drm_post_process_sw_{static,dynamic}_device's d_top_ids,
+ * d_top_scores and d_status unchanged, and its outputs feed the device forms of drm_pair_hits, drm_hit_mapq,
+ * drm_pair_mapq and drm_tlen_scan unchanged. Like every handle-based call it makes the handle's device the current
+ * one and leaves it so. */
+int drm_contig_hits_device(const drm_contigs *c, int32_t ref_len, const uint64_t *d_ids, const int32_t *d_scores,
+                           const int32_t *d_cnt, int64_t nreads, int32_t k, uint64_t *d_out_ids,
+                           uint64_t *d_out_spread, int32_t *d_out_scores, int32_t *d_out_contig, int32_t *d_out_cnt,
+                           void *stream);
+
 /* ---------------------------------------------------------------- L2 rerank (the reference's live path)
  * post_process_l2_static (src/utils/post_processor.cpp:1023-1162, called at src/main.cpp:330) ->
  * find_sequences (static) -> Vectorizer::vectorize of the candidate windows -> batch_reranker(k = k_clusters)

@@ -12,6 +12,9 @@
 // reference's omp_set_num_threads(128) at :116). Extra knobs via env: DRM_BUILD_DEVICE (auto | gpu | cpu),
 // DRM_BUILD_THREADS (host builder threads, default: all cores), DRM_BUILD_SEED (default 0), DRM_DEVICE
 // (the GPU for the encoder and the builder).
+// DRM_CONTIGS=1 (a FASTA at stride 1 only): the windows are all windows of the genome string extract_fasta_sequence
+// makes of the file, not the windows of each contig, so that index id w is position w >> 1 of that string whatever the
+// number of contigs; for a single-contig FASTA that is the same index.
 #include <cstdlib>
 #include <cstring>
 #include <filesystem>
@@ -45,6 +48,13 @@ int main(int argc, char *argv[])
         const int threads = std::getenv("DRM_BUILD_THREADS") ? std::atoi(std::getenv("DRM_BUILD_THREADS")) : 0;
         const uint64_t seed = std::getenv("DRM_BUILD_SEED") ? std::strtoull(std::getenv("DRM_BUILD_SEED"), 0, 10) : 0;
 
+        const bool contigs = std::getenv("DRM_CONTIGS") && std::atoi(std::getenv("DRM_CONTIGS")) != 0;
+        const std::string ext = std::filesystem::path(ref_file).extension().string();
+        if (contigs && ext != ".fna" && ext != ".fasta" && ext != ".fa")
+            throw drm::Error(DRM_ERR_ARG, "DRM_CONTIGS=1 needs a FASTA reference (.fna, .fasta, .fa), not " + ref_file);
+        if (contigs && stride != 1)
+            throw drm::Error(DRM_ERR_UNSUPPORTED, "DRM_CONTIGS=1 needs stride 1, not " + std::to_string(stride));
+
         std::vector<float> emb;
         size_t n = 0, dim = 128;
         if (std::filesystem::path(ref_file).extension() == ".npy") {
@@ -61,7 +71,28 @@ int main(int argc, char *argv[])
             std::memcpy(emb.data(), a.bytes.data(), emb.size() * sizeof(float));
         } else {
             std::vector<std::string> seqs, ids;
-            drm::read_file(ref_file, seqs, ids, ref_len, stride, false);
+            if (contigs) {
+                // every window of the genome string at stride 1, so that id >> 1 is a position in it whatever the
+                // number of contigs; the windows that leave their contig are dropped after the rerank (drm_contig_hits)
+                const std::vector<drm::FastaContig> table = drm::fasta_contigs(ref_file);
+                const std::string g = drm::extract_fasta_sequence(ref_file);
+                size_t bases = 0, inside = 0;
+                for (const drm::FastaContig &c : table) {
+                    bases += (size_t)c.len;
+                    inside += (size_t)c.len >= ref_len ? (size_t)c.len - ref_len + 1 : 0;
+                }
+                const size_t nw = g.size() >= ref_len && ref_len > 0 ? g.size() - ref_len + 1 : 0;
+                for (size_t w = 0; w < nw; ++w) {
+                    const std::string win = g.substr(w, ref_len);
+                    seqs.push_back("<" + win + ">");
+                    seqs.push_back("<" + drm::reverse_complement(win) + ">");
+                }
+                std::cout << "[BUILD INDEX] DRM_CONTIGS: " << table.size() << " contigs, " << bases << " bases in a "
+                          << g.size() << "-base genome string; " << nw - std::min(inside, nw) << " of " << nw
+                          << " window positions straddle a contig end or touch a gap" << std::endl;
+            } else {
+                drm::read_file(ref_file, seqs, ids, ref_len, stride, false);
+            }
             if (seqs.empty()) {
                 std::cerr << "No sequences found in file: " << ref_file << std::endl;
                 return 1;

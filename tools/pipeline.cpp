@@ -27,6 +27,10 @@
 // DRM_SAM_MAPQ=1 (with use_dynamic=1 use_streaming=1 DRM_SAM_CIGAR=1, one device) replaces the constant MAPQ 60 by the
 // locus scan of each read's rerank rows (drm_hit_mapq; for pairs drm_pair_mapq and drm_pair_mapq_rescued), with
 // DRM_MAPQ_MIN=n and DRM_MAPQ_SPAN=n; the SW rerank then runs whatever the stride, as with DRM_MATES.
+// DRM_CONTIGS=1 (with use_dynamic=1 use_streaming=1 DRM_SAM_CIGAR=1, sequence queries, one device, an index of stride 1
+// built with DRM_CONTIGS=1) tells the reference's contigs apart: drm_contig_hits drops every rerank row whose window
+// does not lie inside one contig, the pair-level kernels get its spread ids, and the SAM carries one @SQ per contig,
+// the contig's name in RNAME and positions that count from the contig's start.
 // Sequence inputs are embedded by the reference's GRU model on the GPU (drm_vectorize) when
 // DRM_ENCODER names it (.xml IR or .drmenc) or when the reference's models/ path exists in the working
 // directory (Config::Inference::MODEL_PATH); otherwise by the deterministic 3-mer stand-in. The rerank is
@@ -92,8 +96,44 @@ struct BlockAlignments {
                 regions ? region_len.data() : nullptr};
     }
 
+    // DRM_CONTIGS, the flank guard: row_contig[i * k + j] is the row's contig in `table`. A row keeps its flank iff its
+    // region, as drm_sw_align_region clamps it to the genome, lies inside that contig; the others are aligned with flank
+    // 0, their window being inside the contig by construction.
     void align(drm_refs *rt, const uint64_t *ids, const int32_t *cnt, size_t m, size_t k, const uint8_t *queries,
-               const int32_t *q_len, int32_t q_stride, int32_t ref_len, const AffineMode *affine)
+               const int32_t *q_len, int32_t q_stride, int32_t ref_len, const AffineMode *affine,
+               const drm_contigs *table = nullptr, const int32_t *row_contig = nullptr)
+    {
+        rec.assign(m * k, drm_sw_alignment{0, 0, 0, 0, 0, 0, 0, 1});
+        off.assign(m * k, 0);
+        ops.clear();
+        if (affine) {
+            region_start.assign(m * k, 0);
+            region_len.assign(m * k, 0);
+        }
+        if (!affine || !table || affine->flank == 0) {
+            align_rows(rt, ids, cnt, m, k, queries, q_len, q_stride, ref_len, affine, nullptr);
+            return;
+        }
+        std::vector<uint8_t> inside(m * k, 0);
+        for (size_t i = 0; i < m; ++i)
+            for (size_t j = 0; j < k && (int64_t)j < (int64_t)cnt[i]; ++j) {
+                int64_t start = 0;
+                int32_t len = 0, rev = 0, t = -1;
+                check(drm_sw_align_region(rt, ids[i * k + j], affine->flank, &start, &len, &rev));
+                check(drm_contigs_find(table, start, len, &t));
+                inside[i * k + j] = t >= 0 && t == row_contig[i * k + j];
+            }
+        const AffineMode bare{affine->scoring, 0};
+        for (uint8_t &x : inside) // the rows that keep their flank, then the others with none
+            x = x ? 1 : 2;
+        align_rows(rt, ids, cnt, m, k, queries, q_len, q_stride, ref_len, affine, inside.data(), 1);
+        align_rows(rt, ids, cnt, m, k, queries, q_len, q_stride, ref_len, &bare, inside.data(), 2);
+    }
+
+    // the rows of the block whose pick[row] == want (pick null: every row), into rec / off / ops / the regions
+    void align_rows(drm_refs *rt, const uint64_t *ids, const int32_t *cnt, size_t m, size_t k, const uint8_t *queries,
+                    const int32_t *q_len, int32_t q_stride, int32_t ref_len, const AffineMode *affine,
+                    const uint8_t *pick, uint8_t want = 0)
     {
         constexpr int32_t kStride = 16;
         constexpr size_t kChunk = (size_t)1 << 20; // pairs per launch
@@ -116,13 +156,13 @@ struct BlockAlignments {
         std::vector<int64_t> pq, row;
         for (size_t i = 0; i < m; ++i)
             for (size_t j = 0; j < k && (int64_t)j < (int64_t)cnt[i]; ++j) {
+                if (pick && pick[i * k + j] != want)
+                    continue;
                 wid.push_back(ids[i * k + j]);
                 pq.push_back((int64_t)i);
                 row.push_back((int64_t)(i * k + j));
             }
         const size_t np = wid.size();
-        rec.assign(m * k, drm_sw_alignment{0, 0, 0, 0, 0, 0, 0, 1});
-        off.assign(m * k, 0);
         std::vector<drm_sw_alignment> r1, r2;
         std::vector<uint32_t> o1, o2;
         pass(wid, pq, kStride, r1, o1);
@@ -136,7 +176,6 @@ struct BlockAlignments {
             }
         const int32_t full = q_stride + ref_len + (affine ? 2 * affine->flank : 0);
         pass(wid2, pq2, full, r2, o2);
-        ops.clear();
         size_t x2 = 0;
         for (size_t p = 0; p < np; ++p) {
             const bool retried = x2 < idx2.size() && idx2[x2] == (int64_t)p;
@@ -148,8 +187,6 @@ struct BlockAlignments {
             ops.insert(ops.end(), o, o + r.n_ops);
         }
         if (affine) {
-            region_start.assign(m * k, 0);
-            region_len.assign(m * k, 0);
             for (size_t p = 0; p < np; ++p) {
                 int32_t rev = 0;
                 check(drm_sw_align_region(rt, wid[p], affine->flank, &region_start[(size_t)row[p]],
@@ -350,6 +387,7 @@ struct Options {
     bool use_streaming = false, is_npy = false;
     bool dyn = false; // windows cut from the genome string on the device
     bool has_affine = false, paired = false, mapq = false;
+    bool contigs = false; // DRM_CONTIGS: the reference's contigs are told apart (Pipeline::contig_stage)
     AffineMode affine_mode{};
     PairMode pair{};
     drm_mapq_params mapq_prm{};
@@ -415,6 +453,27 @@ static Options read_options(int argc, char *argv[], size_t ref_len, size_t strid
         throw drm::Error(DRM_ERR_UNSUPPORTED, "DRM_MATES runs on one device (DRM_DEVICE), not on DRM_DEVICES");
     if (o.mapq && o.devices.size() != 1)
         throw drm::Error(DRM_ERR_UNSUPPORTED, "DRM_SAM_MAPQ runs on one device (DRM_DEVICE), not on DRM_DEVICES");
+    // DRM_CONTIGS=1: everything it needs is checked here, before the index is loaded
+    o.contigs = env_flag("DRM_CONTIGS");
+    if (o.contigs) {
+        if (!use_dynamic || !o.use_streaming)
+            throw drm::Error(DRM_ERR_ARG, "DRM_CONTIGS needs use_dynamic=1 and use_streaming=1: contigs are told apart "
+                                          "in the streamed SAM");
+        if (!cigar)
+            throw drm::Error(DRM_ERR_ARG, "DRM_CONTIGS needs DRM_SAM_CIGAR=1: RNAME and POS come from real alignments");
+        if (o.is_npy)
+            throw drm::Error(DRM_ERR_ARG, "DRM_CONTIGS needs sequence queries, not .npy embeddings");
+        if (o.devices.size() != 1)
+            throw drm::Error(DRM_ERR_UNSUPPORTED, "DRM_CONTIGS runs on one device (DRM_DEVICE), not on DRM_DEVICES");
+        if (stride != 1)
+            throw drm::Error(DRM_ERR_UNSUPPORTED, "DRM_CONTIGS needs an index of stride 1, not " +
+                                                      std::to_string(stride));
+        if (l2_rows)
+            throw drm::Error(DRM_ERR_ARG, "DRM_CONTIGS does not go with DRM_SAM_L2_ROWS=1");
+        if (ref_len < 1 || ref_len > ((size_t)1 << 20))
+            throw drm::Error(DRM_ERR_UNSUPPORTED, "DRM_CONTIGS: ref_len " + std::to_string(ref_len) +
+                                                      " outside [1, 2^20]");
+    }
     if (const char *e = std::getenv("DRM_SAM_BLOCK"))
         o.sam_block = std::max<size_t>(1, std::strtoull(e, nullptr, 10));
     if (!o.is_npy)
@@ -431,7 +490,8 @@ static Options read_options(int argc, char *argv[], size_t ref_len, size_t strid
     o.dyn = use_dynamic && !o.is_npy;
     o.stream_sam = o.use_streaming && o.dyn;
     // DRM_MATES, DRM_SAM_MAPQ: pairing and MAPQ need scores, so the SW rerank runs whatever the stride
-    o.sam_from_search = o.stream_sam && stride == 1 && !o.paired && !o.mapq;
+    // DRM_CONTIGS: the contig stage works on the rerank's rows, so the rerank runs as well
+    o.sam_from_search = o.stream_sam && stride == 1 && !o.paired && !o.mapq && !o.contigs;
     const bool sparse_rows = o.stream_sam && stride > 1 && l2_rows && !o.paired;
     o.header_only = o.stream_sam && stride > 1 && !l2_rows && !o.paired && !o.mapq;
     o.l2_rows = sparse_rows && o.devices.size() == 1 && !o.model.empty();
@@ -503,6 +563,12 @@ struct Pipeline {
     Pinned<int64_t> I;
     Pinned<uint64_t> sw_ids;
     drm_search_stats st{};
+    // DRM_CONTIGS: the reference's contig table, its handle, and per rerank row [nq x k] the spread id and the contig that
+    // contig_stage leaves beside the filtered sw_ids / sw_scores / status
+    std::vector<drm::FastaContig> ctable;
+    drm_contigs *ctg = nullptr;
+    std::vector<uint64_t> spread;
+    std::vector<int32_t> row_contig;
     drm_pair_params pair_prm; // o.pair.prm, with DRM_PAIR_TLEN=auto the estimated window from estimate_tlen on
 
     explicit Pipeline(const Options &opt)
@@ -545,6 +611,10 @@ struct Pipeline {
             std::cout << "[MAIN] Using DYNAMIC fetching for reference sequences" << std::endl;
             genome = drm::extract_fasta_sequence(o.ref_file);
             std::cout << "[MAIN] Loaded a " << genome.size() << " bp genome from " << o.ref_file << std::endl;
+            if (o.contigs) {
+                ctable = drm::fasta_contigs(o.ref_file);
+                std::cout << "[MAIN] DRM_CONTIGS: " << ctable.size() << " contigs" << std::endl;
+            }
         } else if (!o.is_npy) {
             std::cout << "[MAIN] Using STATIC fetching for reference sequences" << std::endl;
             std::vector<std::string> refs, dummy;
@@ -598,6 +668,19 @@ struct Pipeline {
                 check(drm_multi_create(index_file.c_str(), devices.data(), (int)devices.size(), tbl, (int64_t)n_ref,
                                        (int32_t)o.ref_len, (int64_t)o.ref_len, &multi));
             check(drm_multi_get_index_info(multi, &info));
+        }
+        if (o.contigs) {
+            const int64_t want = genome.size() >= o.ref_len ? 2 * (int64_t)(genome.size() - o.ref_len + 1) : 0;
+            if (info.ntotal != want)
+                throw drm::Error(DRM_ERR_ARG, "DRM_CONTIGS: the index holds " + std::to_string(info.ntotal) +
+                                                  " vectors, the genome string of " + o.ref_file + " has " +
+                                                  std::to_string(want) + " windows: rebuild the index with DRM_CONTIGS=1");
+            std::vector<int64_t> starts, lens;
+            for (const drm::FastaContig &c : ctable) {
+                starts.push_back(c.start);
+                lens.push_back(c.len);
+            }
+            check(drm_contigs_create(starts.data(), lens.data(), (int64_t)starts.size(), device, &ctg));
         }
         if (index) // the executor's streams and buffers for this batch, outside the search timing
             check(drm_search_rerank_prepare(index, (int64_t)nq, (int32_t)(o.is_npy ? dim : info.d), o.k_clusters, o.k,
@@ -656,7 +739,27 @@ struct Pipeline {
         I.alloc(nq * kc);
         sw_scores.alloc(o.is_npy ? 0 : nq * k);
         sw_ids.alloc(o.is_npy ? 0 : nq * k);
+        if (o.contigs) {
+            spread.assign(nq * k, ~0ull);
+            row_contig.assign(nq * k, -1);
+        }
     }
+
+    // DRM_CONTIGS, after the search + rerank of reads [lo, lo + m): drm_contig_hits over their rows. The stage's lists and
+    // counts replace the rerank's in sw_ids / sw_scores / status, so that everything downstream reads real ids of rows
+    // inside one contig; the spread ids and the contigs go beside them.
+    void contig_stage(size_t lo, size_t m)
+    {
+        std::vector<uint64_t> ids(m * k);
+        std::vector<int32_t> sc(m * k), cnt(m);
+        check(drm_contig_hits(ctg, (int32_t)o.ref_len, sw_ids.p + lo * k, sw_scores.p + lo * k, status.p + lo, (int64_t)m,
+                              o.k, ids.data(), spread.data() + lo * k, sc.data(), row_contig.data() + lo * k, cnt.data()));
+        std::memcpy(sw_ids.p + lo * k, ids.data(), sizeof(uint64_t) * m * k);
+        std::memcpy(sw_scores.p + lo * k, sc.data(), sizeof(int32_t) * m * k);
+        std::memcpy(status.p + lo, cnt.data(), sizeof(int32_t) * m);
+    }
+    // the ids the pair-level kernels get: the spread ids under DRM_CONTIGS
+    const uint64_t *level_ids() const { return o.contigs ? spread.data() : sw_ids.p; }
 
     // HNSW search (faiss_search(alg_hnsw, embeddings, k_clusters, ef), src/main.cpp:278) streamed into the SW rerank
     // (post_process_sw_static, :333-341) batch by batch: one pass over queries [lo, lo + m) into the output arrays at
@@ -680,9 +783,12 @@ struct Pipeline {
         std::filesystem::create_directories(o.out_dir);
     }
 
-    void align_block(BlockAlignments &ba, const uint64_t *ids, const int32_t *cnt, size_t lo, size_t m, size_t width)
+    // contig: with DRM_CONTIGS the contig of every row, indexed like ids (the flank guard)
+    void align_block(BlockAlignments &ba, const uint64_t *ids, const int32_t *cnt, size_t lo, size_t m, size_t width,
+                     const int32_t *contig = nullptr)
     {
-        ba.align(art, ids, cnt, m, width, qbuf.p + lo * qs, ql.p + lo, (int32_t)qs, (int32_t)o.ref_len, o.affine());
+        ba.align(art, ids, cnt, m, width, qbuf.p + lo * qs, ql.p + lo, (int32_t)qs, (int32_t)o.ref_len, o.affine(),
+                 contig ? ctg : nullptr, contig);
     }
 
     // What the reference's sparse branch writes is only the SAM header: its write_sam_streaming call there
@@ -771,6 +877,8 @@ struct Pipeline {
             std::function<void()> write;
             if (rc == DRM_OK) {
                 try {
+                    if (o.contigs)
+                        contig_stage(lo * per, m * per);
                     write = produce(lo, m);
                 } catch (...) {
                     join();
@@ -801,7 +909,7 @@ struct Pipeline {
     // receive a rescued pair's record and the rescued mate's own score.
     void rescue_block(size_t lo, const std::vector<drm_pair_result> &res, std::vector<uint64_t> &chosen,
                       std::vector<int32_t> &cnt, std::vector<int32_t> &proper, std::vector<drm_pair_result> *after,
-                      std::vector<int32_t> *rescue_score)
+                      std::vector<int32_t> *rescue_score, std::vector<int32_t> *contig)
     {
         const size_t np = res.size();
         auto row_id = [&](size_t read, int32_t j) { return j >= 0 ? sw_ids.p[(lo + read) * k + (size_t)j] : (uint64_t)0; };
@@ -833,6 +941,23 @@ struct Pipeline {
                 continue;
             const drm_rescue_result *rA = slot[2 * p] >= 0 ? &out[(size_t)slot[2 * p]] : nullptr;
             const drm_rescue_result *rB = slot[2 * p + 1] >= 0 ? &out[(size_t)slot[2 * p + 1]] : nullptr;
+            if (o.contigs) {
+                // the rescue guard: a rescued window that is not wholly inside its anchor's contig is no candidate
+                auto guard = [&](const drm_rescue_result *&r, size_t anchor) {
+                    if (!r || r->status != 0)
+                        return;
+                    uint64_t w = 0;
+                    int32_t t = -1;
+                    check(drm_mate_rescue_window(r, prm.ref_len, (int64_t)genome.size(), &w));
+                    check(drm_contigs_find(ctg, (int64_t)(w >> 1), prm.ref_len, &t));
+                    if (t < 0 || t != (*contig)[anchor])
+                        r = nullptr;
+                };
+                guard(rA, 2 * p);
+                guard(rB, 2 * p + 1);
+                if (!rA && !rB)
+                    continue;
+            }
             drm_pair_result r{};
             uint64_t wr = 0;
             check(drm_pair_rescue_choose(&res[p], row_score(2 * p, res[p].j1), row_score(2 * p + 1, res[p].j2),
@@ -843,6 +968,8 @@ struct Pipeline {
             const size_t read = 2 * p + (r.status == 5 ? 1 : 0);
             chosen[read] = wr;
             cnt[read] = 1;
+            if (contig)
+                (*contig)[read] = (*contig)[read ^ 1]; // the guard: inside the anchor's contig
             proper[p] = 1;
             if (after) {
                 (*after)[p] = r;
@@ -890,6 +1017,27 @@ struct Pipeline {
             const uint64_t *ids = static_cast<const uint64_t *>(d_ids.p);
             const int32_t *sc = static_cast<const int32_t *>(d_sc.p), *cnt = static_cast<const int32_t *>(d_cnt.p),
                           *fl = static_cast<const int32_t *>(d_full.p);
+            // DRM_CONTIGS: the contig stage chained on the device, the scan then reads its spread ids, scores and counts
+            struct StageOut { // allocated under DRM_CONTIGS only
+                DeviceMem ids, spread, sc, ctg, cnt;
+                StageOut(size_t rows, size_t reads)
+                    : ids(nullptr, sizeof(uint64_t) * rows), spread(nullptr, sizeof(uint64_t) * rows),
+                      sc(nullptr, sizeof(int32_t) * rows), ctg(nullptr, sizeof(int32_t) * rows),
+                      cnt(nullptr, sizeof(int32_t) * reads)
+                {
+                }
+            };
+            std::unique_ptr<StageOut> so;
+            if (o.contigs) {
+                so.reset(new StageOut(m * k, m));
+                check(drm_contig_hits_device(ctg, ref_len, ids, sc, cnt, (int64_t)m, o.k,
+                                             static_cast<uint64_t *>(so->ids.p), static_cast<uint64_t *>(so->spread.p),
+                                             static_cast<int32_t *>(so->sc.p), static_cast<int32_t *>(so->ctg.p),
+                                             static_cast<int32_t *>(so->cnt.p), nullptr));
+                ids = static_cast<const uint64_t *>(so->spread.p);
+                sc = static_cast<const int32_t *>(so->sc.p);
+                cnt = static_cast<const int32_t *>(so->cnt.p);
+            }
             check(drm_tlen_scan_device(&o.mapq_prm, &tp, ids, sc, cnt, ids + k, sc + k, cnt + 1, fl, fl + 1, (int64_t)np,
                                        o.k, 2, static_cast<drm_tlen_sample *>(d_samples.p),
                                        static_cast<uint32_t *>(d_hist.p), nullptr));
@@ -937,9 +1085,11 @@ struct Pipeline {
         auto proper = std::make_shared<std::vector<int32_t>>(mp, 0);
         auto line_mapq = std::make_shared<std::vector<int32_t>>(o.mapq ? m : 0, 0);
         auto ba = std::make_shared<BlockAlignments>();
+        auto contig = std::make_shared<std::vector<int32_t>>(o.contigs ? m : 0, -1); // of each read's chosen row
+        const uint64_t *lids = level_ids();
         std::vector<drm_pair_result> res(mp);
         check(drm_set_device(device));
-        check(drm_pair_hits(&pair_prm, sw_ids.p + at, sw_scores.p + at, status.p + lo, sw_ids.p + at + k,
+        check(drm_pair_hits(&pair_prm, lids + at, sw_scores.p + at, status.p + lo, lids + at + k,
                             sw_scores.p + at + k, status.p + lo + 1, (int64_t)mp, o.k, 2, res.data()));
         for (size_t p = 0; p < mp; ++p) {
             const int32_t j[2] = {res[p].j1, res[p].j2};
@@ -947,6 +1097,8 @@ struct Pipeline {
                 if (j[t] >= 0) {
                     (*ids)[2 * p + t] = sw_ids.p[(lo + 2 * p + t) * k + (size_t)j[t]];
                     (*cnt)[2 * p + t] = 1;
+                    if (o.contigs)
+                        (*contig)[2 * p + t] = row_contig[(lo + 2 * p + t) * k + (size_t)j[t]];
                 }
             (*proper)[p] = res[p].status == 0;
         }
@@ -957,13 +1109,14 @@ struct Pipeline {
         if (o.mapq) {
             for (size_t r = 0; r < m; ++r)
                 full[r] = untagged_length(qseqs[lo + r]);
-            check(drm_pair_mapq(&pair_prm, &o.mapq_prm, sw_ids.p + at, sw_scores.p + at, status.p + lo,
-                                sw_ids.p + at + k, sw_scores.p + at + k, status.p + lo + 1, full.data(), full.data() + 1,
+            check(drm_pair_mapq(&pair_prm, &o.mapq_prm, lids + at, sw_scores.p + at, status.p + lo,
+                                lids + at + k, sw_scores.p + at + k, status.p + lo + 1, full.data(), full.data() + 1,
                                 res.data(), (int64_t)mp, o.k, 2, pm.data()));
             after = res;
         }
         if (o.pair.rescue)
-            rescue_block(lo, res, *ids, *cnt, *proper, o.mapq ? &after : nullptr, o.mapq ? &rescue_score : nullptr);
+            rescue_block(lo, res, *ids, *cnt, *proper, o.mapq ? &after : nullptr, o.mapq ? &rescue_score : nullptr,
+                         o.contigs ? contig.get() : nullptr);
         if (o.mapq) {
             if (o.pair.rescue)
                 check(drm_pair_mapq_rescued(&o.mapq_prm, after.data(), rescue_score.data(), full.data(), full.data() + 1,
@@ -973,10 +1126,12 @@ struct Pipeline {
                 (*line_mapq)[2 * p + 1] = pm[p].mapq2;
             }
         }
-        align_block(*ba, ids->data(), cnt->data(), lo, m, 1);
-        return [this, lo, mp, ids, cnt, proper, ba, line_mapq] {
+        align_block(*ba, ids->data(), cnt->data(), lo, m, 1, o.contigs ? contig->data() : nullptr);
+        return [this, lo, mp, ids, cnt, proper, ba, line_mapq, contig] {
+            const drm::SamContigs sc{&ctable, contig->data()};
             drm::write_sam_pairs(o.sam_file, lo == 0, "ref", o.ref_len, qseqs, qids, lo, mp, ids->data(), cnt->data(),
-                                 proper->data(), ba->view(), o.mapq ? line_mapq->data() : nullptr);
+                                 proper->data(), ba->view(), o.mapq ? line_mapq->data() : nullptr,
+                                 o.contigs ? &sc : nullptr);
         };
     }
 
@@ -1000,17 +1155,20 @@ struct Pipeline {
                 for (size_t i = 0; i < m; ++i)
                     full[i] = untagged_length(qseqs[lo + i]);
                 check(drm_set_device(device));
-                check(drm_hit_mapq(&o.mapq_prm, rows, sw_scores.p + lo * k, status.p + lo, head.data(), full.data(),
+                const uint64_t *lids = o.contigs ? spread.data() + lo * k : rows; // DRM_CONTIGS: the spread ids
+                check(drm_hit_mapq(&o.mapq_prm, lids, sw_scores.p + lo * k, status.p + lo, head.data(), full.data(),
                                    (int64_t)m, o.k, res.data()));
                 for (size_t i = 0; i < m; ++i)
                     (*line_mapq)[i * kr] = res[i].mapq; // secondary lines print 0
             }
-            align_block(*ba, rows, cnt->data(), lo, m, kr);
+            align_block(*ba, rows, cnt->data(), lo, m, kr, o.contigs ? row_contig.data() + lo * k : nullptr);
         }
         return [this, lo, m, kr, rows, cnt, ba, line_mapq] {
             const drm::SamAlignments av = ba->view();
+            const drm::SamContigs sc{&ctable, o.contigs ? row_contig.data() + lo * k : nullptr};
             drm::write_sam_block(o.sam_file, lo == 0, "ref", o.ref_len, qseqs, qids, lo, m, rows, cnt->data(), kr,
-                                 o.sam_cigar ? &av : nullptr, o.mapq ? line_mapq->data() : nullptr);
+                                 o.sam_cigar ? &av : nullptr, o.mapq ? line_mapq->data() : nullptr,
+                                 o.contigs ? &sc : nullptr);
         };
     }
 
@@ -1113,6 +1271,7 @@ int main(int argc, char *argv[])
         const long search_ms = ms_since(t0);
         if (p.art != p.rt)
             drm_refs_free(p.art);
+        drm_contigs_free(p.ctg);
         drm_refs_free(p.rt); // the free calls take null
         drm_index_free(p.index);
         drm_multi_free(p.multi);
