@@ -1856,6 +1856,96 @@ int drm_sw_align_affine(drm_refs *refs, const drm_sw_scoring *scoring, int32_t f
     });
 }
 
+// ---------------------------------------------------------------------- MD words of aligned pairs (sw_md.hip)
+static drm::MdArgs make_md_args(const drm_refs *refs, int32_t flank, const uint64_t *ids, const int64_t *pq,
+                                int64_t npairs, const uint8_t *q, const int32_t *ql, int32_t q_stride, int64_t nq,
+                                const drm_sw_alignment *rec, const uint32_t *ops, const int64_t *ops_off, drm_sw_md *out,
+                                uint32_t *md, int32_t md_stride)
+{
+    if (!refs)
+        throw Error(DRM_ERR_ARG, "null refs");
+    if (flank < 0 || md_stride < 0)
+        throw Error(DRM_ERR_ARG, "negative flank / md_stride");
+    if (flank > 0 && !refs->dev.genome)
+        throw Error(DRM_ERR_ARG, "a flank needs a genome handle: a window table holds nothing beside its rows");
+    if ((int64_t)refs->dev.ref_len + 2 * (int64_t)flank > drm::kAlignMaxLen)
+        throw Error(DRM_ERR_UNSUPPORTED, "window length " + std::to_string(refs->dev.ref_len) + " + 2 * flank " +
+                                             std::to_string(flank) + " > 256 is not supported by the GPU MD kernel");
+    return drm::MdArgs{make_align_args(refs, ids, pq, npairs, q, ql, q_stride, nq, nullptr, nullptr, 0),
+                       flank, rec, ops, ops_off, out, md, md_stride};
+}
+
+int drm_sw_align_md_device(drm_refs *refs, int32_t flank, const uint64_t *d_window_ids, const int64_t *d_pair_query,
+                           int64_t npairs, const uint8_t *d_queries, const int32_t *d_q_len, int32_t q_stride,
+                           int64_t nq, const drm_sw_alignment *d_rec, const uint32_t *d_ops, const int64_t *d_ops_off,
+                           drm_sw_md *d_out, uint32_t *d_md, int32_t md_stride, void *stream)
+{
+    return guarded([&] {
+        const drm::MdArgs ma = make_md_args(refs, flank, d_window_ids, d_pair_query, npairs, d_queries, d_q_len, q_stride,
+                                            nq, d_rec, d_ops, d_ops_off, d_out, d_md, md_stride);
+        if (npairs == 0)
+            return;
+        require_list_pointers(d_window_ids, d_pair_query, d_out, nq, d_queries, d_q_len, d_md, md_stride);
+        if (!d_rec || !d_ops || !d_ops_off)
+            throw Error(DRM_ERR_ARG, "null argument");
+        DRM_HIP_CHECK(hipSetDevice(refs->dev.device));
+        drm::launch_sw_md(refs->dev, ma, q_stride, (hipStream_t)stream);
+    });
+}
+
+int drm_sw_align_md(drm_refs *refs, int32_t flank, const uint64_t *window_ids, const int64_t *pair_query,
+                    int64_t npairs, const uint8_t *queries, const int32_t *q_len, int32_t q_stride, int64_t nq,
+                    const drm_sw_alignment *rec, const uint32_t *ops, const int64_t *ops_off, drm_sw_md *out,
+                    uint32_t *md, int32_t md_stride)
+{
+    return guarded([&] {
+        drm::MdArgs ma = make_md_args(refs, flank, nullptr, nullptr, npairs, nullptr, nullptr, q_stride, nq, nullptr,
+                                      nullptr, nullptr, nullptr, nullptr, md_stride);
+        if (npairs == 0)
+            return;
+        require_list_pointers(window_ids, pair_query, out, nq, queries, q_len, md, md_stride);
+        if (!rec || !ops_off)
+            throw Error(DRM_ERR_ARG, "null argument");
+        // the words the kernel may read: those of the records it walks (status 0, n_ops within [1, 512])
+        int64_t nwords = 0;
+        for (int64_t p = 0; p < npairs; ++p) {
+            if (ops_off[p] < 0)
+                throw Error(DRM_ERR_ARG, "pair " + std::to_string(p) + ": negative ops_off");
+            if (rec[p].status == 0 && rec[p].n_ops >= 1 && rec[p].n_ops <= drm::kMdMaxOps)
+                nwords = std::max(nwords, ops_off[p] + rec[p].n_ops);
+        }
+        if (nwords > 0 && !ops)
+            throw Error(DRM_ERR_ARG, "null operations");
+        const ListUpload in =
+            upload_list(refs->dev.device, "pair", window_ids, pair_query, npairs, queries, q_len, q_stride, nq);
+        DevBuf<drm_sw_alignment> drec((size_t)npairs);
+        DevBuf<uint32_t> dops((size_t)std::max<int64_t>(nwords, 1));
+        DevBuf<int64_t> doff((size_t)npairs);
+        DevBuf<drm_sw_md> dout((size_t)npairs);
+        DevBuf<uint32_t> dmd((size_t)npairs * (size_t)md_stride);
+        drec.upload(rec);
+        doff.upload(ops_off);
+        if (nwords > 0)
+            DRM_HIP_CHECK(hipMemcpy(dops.p, ops, sizeof(uint32_t) * (size_t)nwords, hipMemcpyHostToDevice));
+        if (dmd.n) // words past a pair's n_words read as 0
+            DRM_HIP_CHECK(hipMemset(dmd.p, 0, sizeof(uint32_t) * dmd.n));
+        ma.base.window_ids = in.ids.p;
+        ma.base.pair_query = in.query_of.p;
+        ma.base.queries = in.queries.p;
+        ma.base.q_len = in.q_len.p;
+        ma.rec = drec.p;
+        ma.ops = dops.p;
+        ma.ops_off = doff.p;
+        ma.out = dout.p;
+        ma.md = dmd.p;
+        drm::launch_sw_md(refs->dev, ma, in.longest, nullptr);
+        DRM_HIP_CHECK(hipDeviceSynchronize());
+        dout.download(out);
+        if (dmd.n)
+            dmd.download(md);
+    });
+}
+
 int drm_sw_align_region(const drm_refs *refs, uint64_t window_id, int32_t flank, int64_t *start, int32_t *len,
                         int32_t *reverse)
 {

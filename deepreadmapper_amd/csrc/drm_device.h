@@ -334,6 +334,22 @@ struct AffineAlignArgs {
 };
 void launch_sw_align_affine(const DeviceRefs &refs, AffineAlignArgs a, int max_qlen, hipStream_t stream);
 
+// The MD words of aligned pairs (sw_md.hip; drm_sw_align_md): one wave per pair walks the pair's
+// record and operation words over the region of (window id, flank) as the affine kernel cuts it and the query bytes.
+// base holds the handle's windows, the pairs and the queries; its out / ops / ops_stride are not used.
+struct MdArgs {
+    AlignArgs base;
+    int32_t flank;
+    const drm_sw_alignment *rec; // [npairs]
+    const uint32_t *ops;         // pair p's words start at ops[ops_off[p]]
+    const int64_t *ops_off;      // [npairs]
+    drm_sw_md *out;              // [npairs]
+    uint32_t *md;                // [npairs][md_stride] (value << 4) | kind
+    int32_t md_stride;
+};
+constexpr int kMdMaxOps = 2 * kAlignMaxLen; // a walk over at most 256 + 256 bytes has at most as many runs
+void launch_sw_md(const DeviceRefs &refs, const MdArgs &a, int max_qlen, hipStream_t stream);
+
 // Mate pairing of two reads' reranked hit lists (pair_hits.hip; drm_pair_hits): one wave per
 // pair; pair p's mate-m list is ids_m / scores_m + p * row_step * k with the count cnt_m[p * row_step]. Runs on the
 // current device; throws Error(DRM_ERR_UNSUPPORTED) for k outside [0, kMaxCands].

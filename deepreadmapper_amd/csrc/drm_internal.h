@@ -129,9 +129,17 @@ std::string reverse_complement(const std::string &seq);
 std::vector<std::string> format_fasta(const std::string &data, size_t ref_len, size_t stride, bool lookup_mode);
 // format_fastq (parse_inputs.cpp:843-950): "<"+seq+">" and ids up to ' ', '\t', '/'.
 void format_fastq(const std::string &data, std::vector<std::string> &seqs, std::vector<std::string> &ids);
+// format_fastq that also keeps each record's fourth line (DRM_SAM_QUAL; no reference counterpart: the reference drops
+// it). Throws Error(DRM_ERR_FORMAT) naming the read when a quality line's length differs from its read's.
+void format_fastq_qual(const std::string &data, std::vector<std::string> &seqs, std::vector<std::string> &ids,
+                       std::vector<std::string> &quals);
 // read_file (utils.cpp:188-215) dispatch on extension; .txt = one sequence per non-empty line.
 void read_file(const std::string &path, std::vector<std::string> &seqs, std::vector<std::string> &ids,
                size_t ref_len = 150, size_t stride = 1, bool lookup_mode = false);
+// read_file for a query file, with the quality lines of a .fastq / .fq (format_fastq_qual); any other format leaves
+// quals empty.
+void read_file_qual(const std::string &path, std::vector<std::string> &seqs, std::vector<std::string> &ids,
+                    std::vector<std::string> &quals);
 std::string read_whole_file(const std::string &path);
 // extract_FASTA_sequence (parse_inputs.cpp:174-220): skip the first line, keep the upper-cased
 // A/C/G/T/N letters of everything after it (later header lines included), drop the rest.
@@ -155,12 +163,17 @@ std::vector<FastaContig> fasta_contigs(const std::string &path);
 // With region_start / region_len set (DRM_SAM_SCORING / DRM_SAM_FLANK: drm_sw_align_affine over the row's flanked
 // region, drm_sw_align_region) the record is relative to genome[region_start[row] ..+ region_len[row]) and the row is
 // formatted by drm_sam_cigar_region's rules; AS is then the affine score.
+// With md set (DRM_SAM_MD: drm_sw_align_md of the same rows) every mapped line ends in MD:Z:<drm_sam_md of the row>,
+// behind NM:i; row r has the record md[r] and its complete words at md_words + md_off[r].
 struct SamAlignments {
     const drm_sw_alignment *rec;
     const uint32_t *ops;
     const int64_t *ops_off;
     const int64_t *region_start = nullptr;
     const int32_t *region_len = nullptr;
+    const drm_sw_md *md = nullptr;
+    const uint32_t *md_words = nullptr;
+    const int64_t *md_off = nullptr;
 };
 // `ctg` (DRM_CONTIGS, with `aln` only; null = the one sequence ref_name): the contig table of the reference and the
 // contig of every row, indexed like ids. The header then holds one @SQ line per contig in file order (SN its name, LN
@@ -173,11 +186,13 @@ struct SamContigs {
 };
 // `mapq` (DRM_SAM_MAPQ, null = "60" on every line): the MAPQ column of the block's rows, mapq[i * k + j] for row j of
 // query i; a row written unmapped prints 0.
+// `quals` (DRM_SAM_QUAL, null or empty = "*" in column 11): the quality line of every query, indexed like query_seqs;
+// it is printed reversed on a line whose SEQ is printed reverse-complemented.
 void write_sam_block(const std::string &path, bool header, const std::string &ref_name, size_t ref_len,
                      const std::vector<std::string> &query_seqs, const std::vector<std::string> &query_ids,
                      size_t q0, size_t nq, const uint64_t *ids, const int32_t *counts, size_t k,
                      const SamAlignments *aln = nullptr, const int32_t *mapq = nullptr,
-                     const SamContigs *ctg = nullptr);
+                     const SamContigs *ctg = nullptr, const std::vector<std::string> *quals = nullptr);
 // The paired form (DRM_MATES, no reference counterpart): the two primary lines of pairs whose reads are queries
 // q0 + 2 * p (mate 1) and q0 + 2 * p + 1 (mate 2). Row r = 2 * p + m of the block carries the read's chosen window
 // ids[r] (counts[r] = 1, or 0 for a read without a hit) and its alignment aln.rec[r] as in the DRM_SAM_CIGAR mode
@@ -189,7 +204,8 @@ void write_sam_block(const std::string &path, bool header, const std::string &re
 void write_sam_pairs(const std::string &path, bool header, const std::string &ref_name, size_t ref_len,
                      const std::vector<std::string> &query_seqs, const std::vector<std::string> &query_ids,
                      size_t q0, size_t npairs, const uint64_t *ids, const int32_t *counts, const int32_t *proper,
-                     const SamAlignments &aln, const int32_t *mapq = nullptr, const SamContigs *ctg = nullptr);
+                     const SamAlignments &aln, const int32_t *mapq = nullptr, const SamContigs *ctg = nullptr,
+                     const std::vector<std::string> *quals = nullptr);
 
 // Mate rescue (include/drm_hip.h, drm_mate_rescue): the region of one anchor id, the one statement of the rule that
 // the host entry points (formats.cpp) and the kernel (mate_rescue.hip) both compile. dlo / dhi are

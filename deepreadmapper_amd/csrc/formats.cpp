@@ -280,6 +280,45 @@ void format_fastq(const std::string &data, std::vector<std::string> &seqs, std::
     }
 }
 
+void format_fastq_qual(const std::string &data, std::vector<std::string> &seqs, std::vector<std::string> &ids,
+                       std::vector<std::string> &quals)
+{
+    format_fastq(data, seqs, ids);
+    // the same line walk: line 4 r + 3 belongs to record r
+    const char *cur = data.data();
+    const char *end = cur + data.size();
+    for (int line = 0; cur < end; ++line) {
+        const char *ls = cur;
+        while (cur < end && *cur != '\n')
+            cur++;
+        if (line % 4 == 3)
+            quals.emplace_back(ls, cur - ls);
+        if (cur < end)
+            cur++;
+    }
+    quals.resize(seqs.size()); // a last record cut off before its quality line fails the length check below
+    for (size_t r = 0; r < seqs.size(); ++r)
+        if (quals[r].size() + 2 != seqs[r].size())
+            throw Error(DRM_ERR_FORMAT, "read " + std::to_string(r) + " (" + (r < ids.size() ? ids[r] : std::string()) +
+                                            ") has " + std::to_string(seqs[r].size() - 2) + " bases and " +
+                                            std::to_string(quals[r].size()) + " quality characters");
+}
+
+void read_file_qual(const std::string &path, std::vector<std::string> &seqs, std::vector<std::string> &ids,
+                    std::vector<std::string> &quals)
+{
+    const std::string ext = std::filesystem::path(path).extension().string();
+    quals.clear();
+    if (ext != ".fastq" && ext != ".fq") {
+        read_file(path, seqs, ids);
+        return;
+    }
+    const std::string data = read_whole_file(path);
+    seqs.clear();
+    ids.clear();
+    format_fastq_qual(data, seqs, ids, quals);
+}
+
 void read_file(const std::string &path, std::vector<std::string> &seqs, std::vector<std::string> &ids,
                size_t ref_len, size_t stride, bool lookup_mode)
 {
@@ -497,11 +536,79 @@ extern "C" int drm_sam_cigar(const drm_sw_alignment *a, const uint32_t *ops, int
                                 (int32_t)(window_id & 1u), pos1, cigar, cigar_cap);
 }
 
+// the MD string of one drm_sw_md record and its words (include/drm_hip.h: drm_sam_md)
+static void sam_md(const drm_sw_md &h, const uint32_t *words, bool rev, std::string &md)
+{
+    using drm::Error;
+    if (h.status != 0)
+        throw Error(DRM_ERR_ARG, h.status == 2 ? "the record's MD words are truncated (status 2): compute the pair again "
+                                                 "with a larger md_stride"
+                                               : "the record holds no MD words (status " + std::to_string(h.status) + ")");
+    if (h.n_words < 1 || !words)
+        throw Error(DRM_ERR_ARG, "an MD stream holds at least one number");
+    const auto &comp = drm::comp_table();
+    md.clear();
+    uint32_t prev = 1; // the kind in front of word x; anything but a number in front of the first
+    for (int32_t x = 0; x < h.n_words; ++x) {
+        const uint32_t w = words[rev ? h.n_words - 1 - x : x], kind = w & 15u, value = w >> 4;
+        if (kind > 2u)
+            throw Error(DRM_ERR_ARG, "MD word " + std::to_string(x) + " is not a number, a mismatch or a deleted base");
+        if (kind == 0u) {
+            if (prev == 0u)
+                throw Error(DRM_ERR_ARG, "MD words " + std::to_string(x - 1) + " and " + std::to_string(x) +
+                                             " are both numbers");
+            md += std::to_string(value);
+        } else {
+            if (x == 0 || x == h.n_words - 1)
+                throw Error(DRM_ERR_ARG, "an MD stream starts and ends with a number");
+            const uint32_t base = !rev ? value : value < 128u ? (uint32_t)(unsigned char)comp[value] : 0u;
+            if (base < 'A' || base > 'Z')
+                throw Error(DRM_ERR_ARG, "MD word " + std::to_string(x) + " holds no base letter");
+            if (kind == 2u && prev != 2u)
+                md += '^';
+            md += (char)base;
+        }
+        prev = kind;
+    }
+}
+
+extern "C" int drm_sam_md(const drm_sw_md *h, const uint32_t *words, int32_t reverse, char *md, int32_t md_cap)
+{
+    try {
+        if (!h || !md)
+            throw drm::Error(DRM_ERR_ARG, "null argument");
+        std::string s;
+        sam_md(*h, words, reverse != 0, s);
+        if ((int64_t)s.size() + 1 > (int64_t)md_cap)
+            throw drm::Error(DRM_ERR_ARG, "md_cap " + std::to_string(md_cap) + " is too small for " +
+                                              std::to_string(s.size() + 1) + " bytes");
+        std::memcpy(md, s.c_str(), s.size() + 1);
+        return DRM_OK;
+    } catch (const drm::Error &e) {
+        drm::set_last_error(e.what());
+        return e.code;
+    } catch (const std::exception &e) {
+        drm::set_last_error(e.what());
+        return DRM_ERR_ARG;
+    }
+}
+
+// DRM_SAM_MD: "\tMD:Z:<string>" of a mapped row, nothing when the block carries no MD records
+static void append_md_tag(std::string &buf, const drm::SamAlignments &aln, size_t row, bool rev)
+{
+    if (!aln.md)
+        return;
+    std::string md;
+    sam_md(aln.md[row], aln.md_words + aln.md_off[row], rev, md);
+    buf += "\tMD:Z:" + md;
+}
+
 // one row of the DRM_SAM_CIGAR mode: real POS / CIGAR, SEQ on the forward strand, AS and NM; a hit without an
 // alignment is written as unmapped
 static void append_aligned_row(std::string &buf, const std::string &qname, int flag, const std::string &ref_name,
                                size_t ref_len, const std::string &tagged, uint64_t sid,
-                               const drm::SamAlignments &aln, size_t row, const int32_t *mapq, int64_t contig_start = 0)
+                               const drm::SamAlignments &aln, size_t row, const int32_t *mapq, int64_t contig_start = 0,
+                               const std::string *qual = nullptr)
 {
     const drm_sw_alignment &a = aln.rec[row];
     // the read is the query without format_fastq's tags (an untagged .txt query is the read itself)
@@ -530,10 +637,12 @@ static void append_aligned_row(std::string &buf, const std::string &qname, int f
     buf += cigar;
     buf += "\t*\t0\t0\t";
     buf += clean.empty() ? std::string("*") : (flag & 16) ? drm::reverse_complement(clean) : clean;
-    buf += "\t*";
+    buf += '\t';
+    buf += !qual || qual->empty() ? std::string("*") : (flag & 16) ? std::string(qual->rbegin(), qual->rend()) : *qual;
     if (a.status != 1) {
         buf += "\tAS:i:" + std::to_string(a.score);
         buf += "\tNM:i:" + std::to_string(a.nm);
+        append_md_tag(buf, aln, row, (sid & 1u) != 0);
     }
     buf += '\n';
 }
@@ -554,8 +663,11 @@ static void sam_header(std::ofstream &out, const std::string &ref_name, size_t r
 void drm::write_sam_block(const std::string &path, bool header, const std::string &ref_name, size_t ref_len,
                           const std::vector<std::string> &query_seqs, const std::vector<std::string> &query_ids,
                           size_t q0, size_t nq, const uint64_t *ids, const int32_t *counts, size_t k,
-                          const SamAlignments *aln, const int32_t *mapq, const SamContigs *ctg)
+                          const SamAlignments *aln, const int32_t *mapq, const SamContigs *ctg,
+                          const std::vector<std::string> *quals)
 {
+    if (quals && quals->empty())
+        quals = nullptr;
     if (ctg && !aln)
         throw Error(DRM_ERR_ARG, "a contig table needs the rows' alignments");
     std::ofstream out(path, header ? std::ios::out : std::ios::app);
@@ -572,6 +684,8 @@ void drm::write_sam_block(const std::string &path, bool header, const std::strin
         const std::string qname = (g < query_ids.size() && !query_ids[g].empty()) ? query_ids[g]
                                                                                   : "S1/" + std::to_string(g + 1) + "/0";
         const std::string cigar = std::to_string(clean.size()) + "M";
+        const std::string *qual = quals ? &(*quals)[g] : nullptr;
+        const std::string qual_col = qual && !qual->empty() ? *qual : std::string("*");
         for (int j = 0; j < counts[i] && (size_t)j < k; ++j) {
             const uint64_t sid = ids[i * k + (size_t)j];
             int flag = j == 0 ? 0 : 256; // primary / secondary
@@ -580,12 +694,12 @@ void drm::write_sam_block(const std::string &path, bool header, const std::strin
             if (ctg) {
                 const FastaContig &c = (*ctg->table)[(size_t)ctg->row_contig[i * k + (size_t)j]];
                 append_aligned_row(buf, qname, flag, c.name, ref_len, query_seqs[g], sid, *aln, i * k + (size_t)j, mapq,
-                                   c.start);
+                                   c.start, qual);
                 continue;
             }
             if (aln) {
                 append_aligned_row(buf, qname, flag, ref_name, ref_len, query_seqs[g], sid, *aln, i * k + (size_t)j,
-                                   mapq);
+                                   mapq, 0, qual);
                 continue;
             }
             buf += qname;
@@ -600,11 +714,14 @@ void drm::write_sam_block(const std::string &path, bool header, const std::strin
             buf += '\t';
             buf += cigar;
             buf += "\t*\t0\t0\t";
-            buf += clean;
-            buf += "\t*\n";
+            buf += clean; // as read, also under flag 16: so is the quality line
+            buf += '\t';
+            buf += qual_col;
+            buf += '\n';
         }
         if (ctg && counts[i] < 1) // DRM_CONTIGS: a read without a row inside a contig is written unmapped
-            buf += qname + "\t4\t*\t0\t0\t*\t*\t0\t0\t" + (clean.empty() ? std::string("*") : clean) + "\t*\n";
+            buf += qname + "\t4\t*\t0\t0\t*\t*\t0\t0\t" + (clean.empty() ? std::string("*") : clean) + "\t" + qual_col +
+                   "\n";
         if (buf.size() > (1u << 22)) {
             out << buf;
             buf.clear();
@@ -987,8 +1104,11 @@ extern "C" int drm_tlen_estimate(const uint32_t *hist_row, int32_t nbins, int32_
 void drm::write_sam_pairs(const std::string &path, bool header, const std::string &ref_name, size_t ref_len,
                           const std::vector<std::string> &query_seqs, const std::vector<std::string> &query_ids,
                           size_t q0, size_t npairs, const uint64_t *ids, const int32_t *counts, const int32_t *proper,
-                          const SamAlignments &aln, const int32_t *mapq, const SamContigs *ctg)
+                          const SamAlignments &aln, const int32_t *mapq, const SamContigs *ctg,
+                          const std::vector<std::string> *quals)
 {
+    if (quals && quals->empty())
+        quals = nullptr;
     std::ofstream out(path, header ? std::ios::out : std::ios::app);
     if (!out.is_open())
         throw Error(DRM_ERR_IO, "Failed to open SAM file: " + path);
@@ -1058,10 +1178,15 @@ void drm::write_sam_pairs(const std::string &path, bool header, const std::strin
             buf += '\t';
             buf += clean[m].empty() ? std::string("*")
                                     : (in[m].mapped && in[m].reverse) ? drm::reverse_complement(clean[m]) : clean[m];
-            buf += "\t*";
+            const std::string *qual = quals ? &(*quals)[q0 + 2 * p + (size_t)m] : nullptr;
+            buf += '\t';
+            buf += !qual || qual->empty()           ? std::string("*")
+                   : (in[m].mapped && in[m].reverse) ? std::string(qual->rbegin(), qual->rend())
+                                                     : *qual;
             if (in[m].mapped) {
                 buf += "\tAS:i:" + std::to_string(aln.rec[2 * p + (size_t)m].score);
                 buf += "\tNM:i:" + std::to_string(aln.rec[2 * p + (size_t)m].nm);
+                append_md_tag(buf, aln, 2 * p + (size_t)m, in[m].reverse != 0);
             }
             buf += '\n';
         }

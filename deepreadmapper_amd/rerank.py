@@ -375,6 +375,65 @@ def sam_cigar(record, ops, q_len, ref_len, window_id, tags=(1, 1)):
                            int(window_id))
 
 
+# ------------------------------------------------------------------------------------------- MD words
+# drm_sw_md (include/drm_hip.h)
+SW_MD_DTYPE = np.dtype([(f, np.int32) for f in ("n_words", "n_match", "n_mismatch", "n_ins", "n_del", "status")])
+
+
+def sw_align_md_arrays(table, window_ids, pair_query, query_seqs, records, ops, flank=0, md_stride=16):
+    """The MD words of aligned pairs (drm_sw_align_md): pair p is window window_ids[p] against query pair_query[p] as
+    in sw_align_arrays / sw_align_affine_arrays, `records` and `ops` what one of them returned for the same pairs
+    (a SW_ALIGNMENT_DTYPE array and one operation list per pair) and `flank` the flank it aligned with. Returns
+    (md_records, words): a structured array (SW_MD_DTYPE) and, per pair, its MD words ((value << 4) | kind: 0 a run of
+    matches, 1 a mismatch, 2 a deleted base, the value of the last two being the reference byte). Pairs with more than
+    md_stride words (status 2) are computed again with a stride that cannot overflow, so every returned status is 0,
+    1 or 3."""
+    wid = np.ascontiguousarray(window_ids, dtype=np.uint64)
+    pq = np.ascontiguousarray(pair_query, dtype=np.int64)
+    if wid.shape != pq.shape or wid.ndim != 1:
+        raise ValueError("window_ids and pair_query must be 1-d arrays of one length")
+    rec = np.ascontiguousarray(records, dtype=SW_ALIGNMENT_DTYPE)
+    if rec.shape != wid.shape or len(ops) != len(wid):
+        raise ValueError("one record and one operation list per pair")
+    qbuf, qlen = query_seqs if isinstance(query_seqs, tuple) else pack_queries(query_seqs)
+    lists = [np.ascontiguousarray(o, dtype=np.uint32).ravel() for o in ops]
+    off = np.zeros(len(wid), dtype=np.int64)
+    if len(lists) > 1:
+        off[1:] = np.cumsum([len(o) for o in lists[:-1]])
+    flat = np.concatenate(lists + [np.zeros(1, dtype=np.uint32)])
+
+    def call(sel, stride):
+        h = np.zeros(len(sel), dtype=SW_MD_DTYPE)
+        words = np.zeros((len(sel), stride), dtype=np.uint32)
+        w, q, r, o = (np.ascontiguousarray(x[sel]) for x in (wid, pq, rec, off))
+        check(lib().drm_sw_align_md(table.handle, int(flank), ptr(w), ptr(q), len(sel), ptr(qbuf), ptr(qlen),
+                                    qbuf.shape[1], len(qlen), ptr(r), ptr(flat), ptr(o), ptr(h),
+                                    ptr(words) if words.size else None, int(stride)))
+        return h, words
+    every = np.arange(len(wid))
+    h, words = call(every, int(md_stride))
+    out = [words[p, :min(int(h["n_words"][p]), int(md_stride))].copy() for p in every]
+    again = np.flatnonzero(h["status"] == 2)
+    if len(again):
+        h2, words2 = call(again, 2 * (int(table.ref_len) + 2 * int(flank)) + 1)
+        for x, p in enumerate(again):
+            h[p] = h2[x]
+            out[p] = words2[x, :int(h2["n_words"][x])].copy()
+    return h, out
+
+
+def sam_md(md_record, words, reverse):
+    """The MD:Z string of one pair's MD record and words (drm_sam_md), on the forward strand when `reverse` says the
+    pair's region was a reverse complement."""
+    h = np.zeros(1, dtype=SW_MD_DTYPE)
+    h[0] = tuple(int(md_record[f]) for f in SW_MD_DTYPE.names)
+    w = np.ascontiguousarray(words, dtype=np.uint32)
+    cap = 12 * (len(w) + 1) + 1
+    buf = C.create_string_buffer(cap)
+    check(lib().drm_sam_md(ptr(h), ptr(w) if w.size else None, int(bool(reverse)), buf, cap))
+    return buf.value.decode()
+
+
 # ------------------------------------------------------------------------------------------- L2 rerank
 def embed_windows(table, encoder, stream=None):
     """Fill the table's device embedding of every window with the read encoder (drm_refs_embed): the rows the

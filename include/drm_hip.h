@@ -398,6 +398,63 @@ int drm_sam_cigar_region(const drm_sw_alignment *a, const uint32_t *ops, int32_t
                          int32_t tag_postfix, int64_t region_start, int32_t region_len, int32_t reverse,
                          int64_t *pos1, char *cigar, int32_t cigar_cap);
 
+/* ---------------------------------------------------------------- MD: the reference bases under an alignment
+ * Which columns of an alignment differ and what the reference holds there, for the SAM MD:Z tag. The reference prints
+ * no tags (src/utils/utils.cpp:380-384), so this text is the definition. It is computed for pair p from the pair
+ * itself (window id, query index), its drm_sw_alignment record and its operation words, all as drm_sw_align or
+ * drm_sw_align_affine left them.
+ * Target bytes: the region exactly as drm_sw_align_affine defines it for (window id, flank): a table row, or
+ *   genome[max(0, pos - flank), min(glen, pos + ref_len + flank)), reverse-complemented as a whole with comp_table for
+ *   an odd id, empty past the genome end. With flank 0 this is drm_sw_align's window. Equality is raw byte equality
+ *   between a region byte and a query byte, the aligners' own rule (N against N matches, a tag matches no base).
+ * Walk the operations forward from (ref_begin, q_begin) with a counter `run` of matching columns, 0 at the start:
+ *   M column, equal bytes:    run += 1.
+ *   M column, unequal bytes:  emit the number run, run = 0, then emit one mismatch word with the region byte.
+ *   I operation:              skip its query bytes, emit nothing: a run continues across an insertion.
+ *   D operation of n bytes:   emit the number run (also when it is 0), run = 0, then n deleted-base words with the
+ *                             region bytes.
+ *   after the last operation: emit the number run.
+ * Words are (value << 4) | kind: kind 0 a number (value = the run length), 1 a mismatch, 2 a deleted base (value = the
+ * region byte). The stream starts and ends with a number, two numbers are never adjacent, and the word count is
+ * 2 * mismatches + D operations + deleted bases + 1 (a number in front of every mismatch and every D operation, and
+ * one at the end) <= 2 * region length + 1 <= 513. This is samtools calmd's token rule: D, I, D gives "^AC0^GT".
+ * Per pair: n_words, the counts of matching and mismatching M columns, of inserted and of deleted bases, and status
+ *   0 done;
+ *   1 the record holds no alignment (its status is 1), or the region or the query is empty: every other field is 0;
+ *   2 done, but n_words > md_stride: the first md_stride words are stored and n_words is the full count (retry those
+ *     pairs as a sub-list with a larger stride; md_stride = 2 * (ref_len + 2 * flank) + 1 never overflows);
+ *   3 the record and its words describe no walk inside this region and query: every other field is 0. Raised by a
+ *     record status other than 0 and 1 (2: its words are incomplete), n_ops outside [1, 512], an operation kind above
+ *     2 or a zero length, a negative ref_begin or q_begin, ref_begin > ref_end, ref_end past the region, q_end past
+ *     the query, or the words' reference or query span differing from ref_end - ref_begin or q_end - q_begin.
+ * Status 1 is decided before status 3. Whatever a record says, operation words are read only inside
+ * ops[ops_off[p] .. + min(n_ops, 512)) and only when the record's status is 0, and no byte is read outside the region
+ * and the query. For records the aligners produced, n_mismatch + n_ins + n_del == nm. */
+typedef struct {
+    int32_t n_words, n_match, n_mismatch, n_ins, n_del, status;
+} drm_sw_md;
+/* Pairs, queries, flank limits and argument errors as for drm_sw_align_affine (flank 0 on a window table; a region or
+ * a query above 256 bytes is DRM_ERR_UNSUPPORTED; a negative flank, md_stride or ops_off[p] is DRM_ERR_ARG). rec[npairs];
+ * pair p's words start at ops[ops_off[p]] (p * ops_stride for the aligner's strided buffer); out[npairs],
+ * md [npairs x md_stride], words past n_words read as 0. Host pointers. */
+int drm_sw_align_md(drm_refs *refs, int32_t flank, const uint64_t *window_ids, const int64_t *pair_query,
+                    int64_t npairs, const uint8_t *queries, const int32_t *q_len, int32_t q_stride, int64_t nq,
+                    const drm_sw_alignment *rec, const uint32_t *ops, const int64_t *ops_off, drm_sw_md *out,
+                    uint32_t *md, int32_t md_stride);
+/* Device-buffer form, enqueued on `stream`; query lengths are bounded by q_stride (<= 256), a pair_query outside
+ * [0, nq) is an empty query (status 1), and ops_off is not checked. */
+int drm_sw_align_md_device(drm_refs *refs, int32_t flank, const uint64_t *d_window_ids, const int64_t *d_pair_query,
+                           int64_t npairs, const uint8_t *d_queries, const int32_t *d_q_len, int32_t q_stride,
+                           int64_t nq, const drm_sw_alignment *d_rec, const uint32_t *d_ops, const int64_t *d_ops_off,
+                           drm_sw_md *d_out, uint32_t *d_md, int32_t md_stride, void *stream);
+/* Host only: the MD string of one pair (status 0, words[0 .. n_words) complete): numbers in decimal, a mismatch as its
+ * letter, a run of consecutive deleted-base words as "^" and their letters. reverse != 0: the region was a reverse
+ * complement, so the words are taken in reverse order and every base is complemented (A<->T, C<->G, N->N), which gives
+ * MD on the forward strand as drm_sam_cigar_region gives the CIGAR.
+ * DRM_ERR_ARG: status != 0, a kind above 2, a base that is not 'A'..'Z' after the complement, a stream that does not
+ * start and end with a number or holds two adjacent numbers, or md_cap too small for the string + NUL. */
+int drm_sam_md(const drm_sw_md *h, const uint32_t *words, int32_t reverse, char *md, int32_t md_cap);
+
 /* ---------------------------------------------------------------- Mate pairing (paired-end reads)
  * Which hit of mate 1 and which hit of mate 2 belong to one fragment. The reference maps single reads only (its SAM
  * prints "* 0 0" in RNEXT / PNEXT / TLEN), so this text is the definition.

@@ -31,6 +31,10 @@
 // built with DRM_CONTIGS=1) tells the reference's contigs apart: drm_contig_hits drops every rerank row whose window
 // does not lie inside one contig, the pair-level kernels get its spread ids, and the SAM carries one @SQ per contig,
 // the contig's name in RNAME and positions that count from the contig's start.
+// DRM_SAM_MD=1 (with DRM_SAM_CIGAR=1) appends MD:Z:<string> behind NM:i on every mapped line: a GPU pass over the rows'
+// records and operation words (drm_sw_align_md), then drm_sam_md on the writer thread.
+// DRM_SAM_QUAL=1 keeps the quality lines of .fastq / .fq queries (and DRM_MATES) and prints them in column 11, reversed
+// on a line whose SEQ is reverse-complemented; a quality line of another length than its read ends the run.
 // Sequence inputs are embedded by the reference's GRU model on the GPU (drm_vectorize) when
 // DRM_ENCODER names it (.xml IR or .drmenc) or when the reference's models/ path exists in the working
 // directory (Config::Inference::MODEL_PATH); otherwise by the deterministic 3-mer stand-in. The rerank is
@@ -89,11 +93,17 @@ struct BlockAlignments {
     std::vector<uint32_t> ops;
     std::vector<int64_t> off, region_start;
     std::vector<int32_t> region_len;
+    // DRM_SAM_MD=1: the MD records and words of the same rows (drm_sw_align_md), by the same two-pass rule
+    bool want_md = false;
+    std::vector<drm_sw_md> md;
+    std::vector<uint32_t> md_words;
+    std::vector<int64_t> md_off;
     drm::SamAlignments view() const
     {
         const bool regions = !region_start.empty();
         return {rec.data(), ops.data(), off.data(), regions ? region_start.data() : nullptr,
-                regions ? region_len.data() : nullptr};
+                regions ? region_len.data() : nullptr, want_md ? md.data() : nullptr,
+                want_md ? md_words.data() : nullptr, want_md ? md_off.data() : nullptr};
     }
 
     // DRM_CONTIGS, the flank guard: row_contig[i * k + j] is the row's contig in `table`. A row keeps its flank iff its
@@ -106,6 +116,11 @@ struct BlockAlignments {
         rec.assign(m * k, drm_sw_alignment{0, 0, 0, 0, 0, 0, 0, 1});
         off.assign(m * k, 0);
         ops.clear();
+        if (want_md) {
+            md.assign(m * k, drm_sw_md{0, 0, 0, 0, 0, 1});
+            md_off.assign(m * k, 0);
+            md_words.clear();
+        }
         if (affine) {
             region_start.assign(m * k, 0);
             region_len.assign(m * k, 0);
@@ -192,6 +207,59 @@ struct BlockAlignments {
                 check(drm_sw_align_region(rt, wid[p], affine->flank, &region_start[(size_t)row[p]],
                                           &region_len[(size_t)row[p]], &rev));
             }
+        }
+        if (!want_md)
+            return;
+        // DRM_SAM_MD: the MD words of the rows just aligned, over the pass's own flank: 16 words per row first, then
+        // the rows that hold more (status 2) at the stride that cannot overflow
+        const int32_t flank = affine ? affine->flank : 0;
+        auto md_pass = [&](const std::vector<uint64_t> &w, const std::vector<int64_t> &q,
+                           const std::vector<drm_sw_alignment> &r, const std::vector<int64_t> &o, int32_t stride,
+                           std::vector<drm_sw_md> &h, std::vector<uint32_t> &words) {
+            h.resize(w.size());
+            words.resize(w.size() * (size_t)stride);
+            for (size_t c = 0; c < w.size(); c += kChunk) {
+                const int64_t nc = (int64_t)std::min(kChunk, w.size() - c);
+                check(drm_sw_align_md(rt, flank, w.data() + c, q.data() + c, nc, queries, q_len, q_stride, (int64_t)m,
+                                      r.data() + c, ops.data(), o.data() + c, h.data() + c,
+                                      words.data() + c * (size_t)stride, stride));
+            }
+        };
+        std::vector<drm_sw_alignment> mr(np), mr2;
+        std::vector<int64_t> mo(np), mo2;
+        for (size_t p = 0; p < np; ++p) {
+            mr[p] = rec[(size_t)row[p]];
+            mo[p] = off[(size_t)row[p]];
+        }
+        std::vector<drm_sw_md> h1, h2;
+        std::vector<uint32_t> w1, w2;
+        md_pass(wid, pq, mr, mo, kStride, h1, w1);
+        wid2.clear();
+        pq2.clear();
+        idx2.clear();
+        for (size_t p = 0; p < np; ++p)
+            if (h1[p].status == 2) {
+                wid2.push_back(wid[p]);
+                pq2.push_back(pq[p]);
+                mr2.push_back(mr[p]);
+                mo2.push_back(mo[p]);
+                idx2.push_back((int64_t)p);
+            }
+        const int32_t md_full = 2 * (ref_len + 2 * flank) + 1;
+        md_pass(wid2, pq2, mr2, mo2, md_full, h2, w2);
+        x2 = 0;
+        for (size_t p = 0; p < np; ++p) {
+            const bool retried = x2 < idx2.size() && idx2[x2] == (int64_t)p;
+            const drm_sw_md &h = retried ? h2[x2] : h1[p];
+            const uint32_t *w = retried ? w2.data() + x2 * (size_t)md_full : w1.data() + p * kStride;
+            x2 += retried;
+            // an aligner's own record and words always describe a walk; anything else is a fault of this program
+            if (h.status != 0 && h.status != 1)
+                throw drm::Error(DRM_ERR_ARG, "drm_sw_align_md: status " + std::to_string(h.status) + " on a row the "
+                                              "aligner produced");
+            md[(size_t)row[p]] = h;
+            md_off[(size_t)row[p]] = (int64_t)md_words.size();
+            md_words.insert(md_words.end(), w, w + h.n_words);
         }
     }
 };
@@ -395,6 +463,8 @@ struct Options {
     // the output mode: the first that holds of header_only, l2_rows, paired, stream_sam; none = the .npy files
     bool stream_sam = false, header_only = false, l2_rows = false;
     bool sam_from_search = false, sam_cigar = false, l2_rows_from_sw = false;
+    bool sam_md = false;   // DRM_SAM_MD: MD:Z behind NM:i on every mapped line of the DRM_SAM_CIGAR modes
+    bool sam_qual = false; // DRM_SAM_QUAL: column 11 from the FASTQ's quality lines
     size_t sam_block = 0; // DRM_SAM_BLOCK, 0 = unset
 
     const AffineMode *affine() const { return has_affine ? &affine_mode : nullptr; }
@@ -474,6 +544,10 @@ static Options read_options(int argc, char *argv[], size_t ref_len, size_t strid
             throw drm::Error(DRM_ERR_UNSUPPORTED, "DRM_CONTIGS: ref_len " + std::to_string(ref_len) +
                                                       " outside [1, 2^20]");
     }
+    o.sam_md = env_flag("DRM_SAM_MD");
+    if (o.sam_md && !cigar)
+        throw drm::Error(DRM_ERR_ARG, "DRM_SAM_MD needs DRM_SAM_CIGAR=1: MD describes a real alignment");
+    o.sam_qual = env_flag("DRM_SAM_QUAL");
     if (const char *e = std::getenv("DRM_SAM_BLOCK"))
         o.sam_block = std::max<size_t>(1, std::strtoull(e, nullptr, 10));
     if (!o.is_npy)
@@ -511,11 +585,15 @@ static int32_t untagged_length(const std::string &tagged)
 }
 
 // DRM_MATES: mate 1 of pair i becomes query 2i, mate 2 query 2i + 1, both under mate 1's name
+// (DRM_SAM_QUAL, quals non-null: the quality lines travel with their reads)
 static void interleave_mates(const std::string &query_file, const std::string &mates, std::vector<std::string> &qseqs,
-                             std::vector<std::string> &qids)
+                             std::vector<std::string> &qids, std::vector<std::string> *quals)
 {
-    std::vector<std::string> seqs2, ids2;
-    drm::read_file(mates, seqs2, ids2);
+    std::vector<std::string> seqs2, ids2, quals2;
+    if (quals)
+        drm::read_file_qual(mates, seqs2, ids2, quals2);
+    else
+        drm::read_file(mates, seqs2, ids2);
     const size_t n1 = qseqs.size(), n2 = seqs2.size();
     auto name = [](const std::vector<std::string> &ids, size_t i) { return i < ids.size() ? ids[i] : std::string(); };
     for (size_t i = 0; i < std::min(n1, n2); ++i)
@@ -534,6 +612,16 @@ static void interleave_mates(const std::string &query_file, const std::string &m
     }
     qseqs.swap(seqs);
     qids.swap(ids);
+    if (quals && (!quals->empty() || !quals2.empty())) { // a mate file without quality lines (.txt) keeps "*"
+        std::vector<std::string> both(2 * n1);
+        for (size_t i = 0; i < n1; ++i) {
+            if (i < quals->size())
+                both[2 * i] = std::move((*quals)[i]);
+            if (i < quals2.size())
+                both[2 * i + 1] = std::move(quals2[i]);
+        }
+        quals->swap(both);
+    }
     std::cout << "[MAIN] Paired mode: " << n1 << " pairs, mates from " << mates << std::endl;
 }
 
@@ -546,6 +634,7 @@ struct Pipeline {
     drm::NpyArray emb;
     size_t nq = 0, dim = 0, qs = 0;
     std::vector<std::string> qseqs, qids;
+    std::vector<std::string> quals; // DRM_SAM_QUAL: the reads' quality lines, empty = "*" on every line
     // reference: the static window table as one fixed-width block, or the genome string
     size_t n_ref = 0;
     std::string table, genome;
@@ -590,13 +679,16 @@ struct Pipeline {
             std::cout << "[MAIN] Loaded " << nq << " embeddings of dimension " << dim << std::endl;
             return true;
         }
-        drm::read_file(o.query_file, qseqs, qids);
+        if (o.sam_qual)
+            drm::read_file_qual(o.query_file, qseqs, qids, quals);
+        else
+            drm::read_file(o.query_file, qseqs, qids);
         if (qseqs.empty()) {
             std::cerr << "No query_sequences found in input file!" << std::endl;
             return false;
         }
         if (o.paired)
-            interleave_mates(o.query_file, o.pair.mates, qseqs, qids);
+            interleave_mates(o.query_file, o.pair.mates, qseqs, qids, o.sam_qual ? &quals : nullptr);
         nq = qseqs.size();
         for (auto &q : qseqs)
             qs = std::max(qs, q.size());
@@ -787,6 +879,7 @@ struct Pipeline {
     void align_block(BlockAlignments &ba, const uint64_t *ids, const int32_t *cnt, size_t lo, size_t m, size_t width,
                      const int32_t *contig = nullptr)
     {
+        ba.want_md = o.sam_md;
         ba.align(art, ids, cnt, m, width, qbuf.p + lo * qs, ql.p + lo, (int32_t)qs, (int32_t)o.ref_len, o.affine(),
                  contig ? ctg : nullptr, contig);
     }
@@ -848,7 +941,7 @@ struct Pipeline {
                 av = ba.view();
             }
             drm::write_sam_block(o.sam_file, lo == 0, "ref", o.ref_len, qseqs, qids, lo, m, l2i.data() + lo * k,
-                                 cnt.data() + lo, k, o.sam_cigar ? &av : nullptr);
+                                 cnt.data() + lo, k, o.sam_cigar ? &av : nullptr, nullptr, nullptr, &quals);
         }
     }
 
@@ -1131,7 +1224,7 @@ struct Pipeline {
             const drm::SamContigs sc{&ctable, contig->data()};
             drm::write_sam_pairs(o.sam_file, lo == 0, "ref", o.ref_len, qseqs, qids, lo, mp, ids->data(), cnt->data(),
                                  proper->data(), ba->view(), o.mapq ? line_mapq->data() : nullptr,
-                                 o.contigs ? &sc : nullptr);
+                                 o.contigs ? &sc : nullptr, &quals);
         };
     }
 
@@ -1168,7 +1261,7 @@ struct Pipeline {
             const drm::SamContigs sc{&ctable, o.contigs ? row_contig.data() + lo * k : nullptr};
             drm::write_sam_block(o.sam_file, lo == 0, "ref", o.ref_len, qseqs, qids, lo, m, rows, cnt->data(), kr,
                                  o.sam_cigar ? &av : nullptr, o.mapq ? line_mapq->data() : nullptr,
-                                 o.contigs ? &sc : nullptr);
+                                 o.contigs ? &sc : nullptr, &quals);
         };
     }
 
