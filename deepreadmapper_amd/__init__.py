@@ -19,6 +19,7 @@ from .pairing import (TLEN_ESTIMATE_FIELDS, TLEN_SAMPLE_DTYPE, tlen_estimate, tl
                       tlen_scan_device)  # (the template-length window from the reads)
 from .mapq import (MAPQ_RESULT_DTYPE, PAIR_MAPQ_RESULT_DTYPE, hit_mapq, hit_mapq_device, mapq_params,  # noqa: F401
                    mapq_value, pair_mapq, pair_mapq_device, pair_mapq_rescued)  # (mapping quality)
+from .loci import LOCI_DROP_DEFAULT, hit_loci, hit_loci_device, loci_params  # noqa: F401  (the locus list of a read)
 from .contigs import ContigTable, contig_hits, contig_hits_device, fasta_contigs  # noqa: F401  (multi-contig references)
 
 __version__ = "0.4.0"

@@ -54,6 +54,7 @@ EXPORTS = [
     "drm_pair_rescue_choose",
     "drm_hit_mapq", "drm_hit_mapq_device", "drm_pair_mapq", "drm_pair_mapq_device", "drm_mapq_value",
     "drm_pair_mapq_rescued",
+    "drm_hit_loci", "drm_hit_loci_device",
     "drm_tlen_scan", "drm_tlen_scan_device", "drm_tlen_estimate",
     "drm_fasta_contigs", "drm_contigs_create", "drm_contigs_free", "drm_contigs_find", "drm_contig_lds_max",
     "drm_contig_hits", "drm_contig_hits_device",
@@ -231,6 +232,8 @@ def lib():
         "drm_pair_mapq_device": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i64, vp, vp]),
         "drm_mapq_value": (C.c_int, [i64, i64, i64, i64, i64, C.POINTER(i32)]),
         "drm_pair_mapq_rescued": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, vp]),
+        "drm_hit_loci": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp]),
+        "drm_hit_loci_device": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
         "drm_tlen_scan": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i64, vp, vp]),
         "drm_tlen_scan_device": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i64, vp, vp, vp]),
         "drm_tlen_estimate": (C.c_int, [vp, i32, i32, vp]),

@@ -2115,6 +2115,81 @@ int drm_hit_mapq(const drm_mapq_params *p, const uint64_t *ids, const int32_t *s
     });
 }
 
+// ---------------------------------------------------------------------- locus list (hit_loci.hip)
+static drm::LociArgs make_loci_args(const drm_mapq_params *mp, const drm_loci_params *lp, const uint64_t *ids,
+                                    const int32_t *scores, const int32_t *cnt, const int32_t *head, const int32_t *full,
+                                    int64_t nreads, int32_t k, drm_mapq_result *out, int32_t *n_loci, int32_t *n_pass,
+                                    uint64_t *loci_ids, int32_t *loci_scores, int32_t *loci_rows, int32_t *loci_size)
+{
+    const drm::MapqArgs m = make_mapq_args(mp, ids, scores, cnt, head, full, nreads, k, out);
+    if (!lp)
+        throw Error(DRM_ERR_ARG, "null locus parameters");
+    if (lp->max_loci < 1)
+        throw Error(DRM_ERR_ARG, "max_loci " + std::to_string(lp->max_loci) + " must be at least 1");
+    if (lp->max_loci > drm::kMaxLoci)
+        throw Error(DRM_ERR_UNSUPPORTED, "max_loci " + std::to_string(lp->max_loci) + " beyond 64: a lane of the wave "
+                                         "keeps one slot");
+    if (lp->drop_pct < 0 || lp->drop_pct > 100)
+        throw Error(DRM_ERR_ARG, "drop_pct " + std::to_string(lp->drop_pct) + " outside [0, 100]");
+    if (nreads > 0 && (!n_loci || !n_pass || !loci_ids || !loci_scores || !loci_rows || !loci_size))
+        throw Error(DRM_ERR_ARG, "null argument");
+    return drm::LociArgs{m, *lp, n_loci, n_pass, loci_ids, loci_scores, loci_rows, loci_size};
+}
+
+int drm_hit_loci_device(const drm_mapq_params *mp, const drm_loci_params *lp, const uint64_t *d_ids,
+                        const int32_t *d_scores, const int32_t *d_cnt, const int32_t *d_head, const int32_t *d_full,
+                        int64_t nreads, int32_t k, drm_mapq_result *d_out, int32_t *d_n_loci, int32_t *d_n_pass,
+                        uint64_t *d_loci_ids, int32_t *d_loci_scores, int32_t *d_loci_rows, int32_t *d_loci_size,
+                        void *stream)
+{
+    return guarded([&] {
+        const drm::LociArgs a = make_loci_args(mp, lp, d_ids, d_scores, d_cnt, d_head, d_full, nreads, k, d_out,
+                                               d_n_loci, d_n_pass, d_loci_ids, d_loci_scores, d_loci_rows, d_loci_size);
+        drm::launch_hit_loci(a, (hipStream_t)stream);
+    });
+}
+
+int drm_hit_loci(const drm_mapq_params *mp, const drm_loci_params *lp, const uint64_t *ids, const int32_t *scores,
+                 const int32_t *cnt, const int32_t *head, const int32_t *full, int64_t nreads, int32_t k,
+                 drm_mapq_result *out, int32_t *n_loci, int32_t *n_pass, uint64_t *loci_ids, int32_t *loci_scores,
+                 int32_t *loci_rows, int32_t *loci_size)
+{
+    return guarded([&] {
+        drm::LociArgs a = make_loci_args(mp, lp, ids, scores, cnt, head, full, nreads, k, out, n_loci, n_pass, loci_ids,
+                                         loci_scores, loci_rows, loci_size);
+        if (nreads == 0)
+            return;
+        check_list_scores(cnt, scores, nreads, 1, k, "read ");
+        const size_t slots = (size_t)nreads * (size_t)lp->max_loci;
+        const HitLists d(ids, scores, cnt, full, (size_t)nreads, k);
+        DevBuf<int32_t> dh(head ? (size_t)nreads : 0);
+        DevBuf<drm_mapq_result> dout((size_t)nreads);
+        DevBuf<int32_t> dn((size_t)nreads), dp((size_t)nreads), dsc(slots), drow(slots), dsz(slots);
+        DevBuf<uint64_t> dids(slots);
+        if (head)
+            dh.upload(head);
+        d.bind(a.m.ids, a.m.scores, a.m.cnt);
+        a.m.head = dh.p;
+        a.m.full = d.full.p;
+        a.m.out = dout.p;
+        a.n_loci = dn.p;
+        a.n_pass = dp.p;
+        a.loci_ids = dids.p;
+        a.loci_scores = dsc.p;
+        a.loci_rows = drow.p;
+        a.loci_size = dsz.p;
+        drm::launch_hit_loci(a, nullptr);
+        DRM_HIP_CHECK(hipDeviceSynchronize());
+        dout.download(out);
+        dn.download(n_loci);
+        dp.download(n_pass);
+        dids.download(loci_ids);
+        dsc.download(loci_scores);
+        drow.download(loci_rows);
+        dsz.download(loci_size);
+    });
+}
+
 int drm_pair_mapq_device(const drm_pair_params *pp, const drm_mapq_params *mp, const uint64_t *d_ids1,
                          const int32_t *d_scores1, const int32_t *d_cnt1, const uint64_t *d_ids2,
                          const int32_t *d_scores2, const int32_t *d_cnt2, const int32_t *d_full1,

@@ -410,6 +410,19 @@ struct PairMapqArgs {
 };
 void launch_pair_mapq(const PairMapqArgs &a, hipStream_t stream);
 
+// Locus list (hit_loci.hip; drm_hit_loci): one wave per read, hit_mapq_kernel's scan keeping the
+// loci it meets, lane j holding slot j. Runs on the current device and throws Error(DRM_ERR_UNSUPPORTED) for k outside
+// [0, kMaxCands] or max_loci outside [1, kMaxLoci].
+constexpr int kMaxLoci = 64; // one slot per lane of the wave
+struct LociArgs {
+    MapqArgs m; // the lists, heads, self scores and the MAPQ records
+    drm_loci_params lp;
+    int32_t *n_loci, *n_pass; // [nreads]
+    uint64_t *loci_ids;       // [nreads][max_loci]
+    int32_t *loci_scores, *loci_rows, *loci_size;
+};
+void launch_hit_loci(const LociArgs &a, hipStream_t stream);
+
 // Template-length scan (tlen_scan.hip; drm_tlen_scan): one wave per pair, the locus scan of each
 // mate's list from its top hit and, where both are confident, one atomic add into the histogram of the pair's class.
 // Runs on the current device and throws Error(DRM_ERR_UNSUPPORTED) for k outside [0, kMaxCands].

@@ -188,11 +188,27 @@ struct SamContigs {
 // query i; a row written unmapped prints 0.
 // `quals` (DRM_SAM_QUAL, null or empty = "*" in column 11): the quality line of every query, indexed like query_seqs;
 // it is printed reversed on a line whose SEQ is printed reverse-complemented.
+// `loci` (DRM_SAM_LOCI, with `aln` only): the rows of a query are its distinct loci (drm_hit_loci's slots, k = max_loci),
+// row 0 the primary; a query without rows is written as one unmapped line (flag 4), as under `ctg`. With `xa`
+// (DRM_SAM_XA) rows 1 .. get no line of their own: the primary line ends in the tag
+//   XA:Z:<RNAME>,<+|-><POS>,<CIGAR>,<NM>;...
+// one entry per such row that holds an alignment, POS 1-based in the contig's own coordinates, the sign the strand,
+// the CIGAR drm_sam_cigar's (drm_sam_cigar_region's over a flanked region); no tag when no entry remains.
 void write_sam_block(const std::string &path, bool header, const std::string &ref_name, size_t ref_len,
                      const std::vector<std::string> &query_seqs, const std::vector<std::string> &query_ids,
                      size_t q0, size_t nq, const uint64_t *ids, const int32_t *counts, size_t k,
                      const SamAlignments *aln = nullptr, const int32_t *mapq = nullptr,
-                     const SamContigs *ctg = nullptr, const std::vector<std::string> *quals = nullptr);
+                     const SamContigs *ctg = nullptr, const std::vector<std::string> *quals = nullptr,
+                     bool loci = false, bool xa = false);
+// The alternates behind an XA:Z tag: those of block row r are ids[r * width + j] for first <= j < counts[r], with their
+// alignments aln->rec[r * width + j] and, under DRM_CONTIGS, their contigs ctg->row_contig[r * width + j].
+struct SamXa {
+    const uint64_t *ids;
+    const int32_t *counts;
+    size_t width, first;
+    const SamAlignments *aln;
+    const SamContigs *ctg;
+};
 // The paired form (DRM_MATES, no reference counterpart): the two primary lines of pairs whose reads are queries
 // q0 + 2 * p (mate 1) and q0 + 2 * p + 1 (mate 2). Row r = 2 * p + m of the block carries the read's chosen window
 // ids[r] (counts[r] = 1, or 0 for a read without a hit) and its alignment aln.rec[r] as in the DRM_SAM_CIGAR mode
@@ -201,11 +217,13 @@ void write_sam_block(const std::string &path, bool header, const std::string &re
 //   mapped:   QNAME FLAG ref POS 60 CIGAR = PNEXT TLEN SEQ * AS:i:<score> NM:i:<nm>
 //   unmapped: QNAME FLAG ref|* POS 60 * =|* PNEXT TLEN SEQ *        (SEQ as read; "*" when neither mate is mapped)
 // `mapq` (null = "60"): mapq[r] for the line of row r; an unmapped mate prints 0.
+// `xa` (DRM_SAM_LOCI, null = no tag): the alternates of row r; a mapped mate's line ends in their XA:Z tag
+// (write_sam_block), and nothing else on the line changes.
 void write_sam_pairs(const std::string &path, bool header, const std::string &ref_name, size_t ref_len,
                      const std::vector<std::string> &query_seqs, const std::vector<std::string> &query_ids,
                      size_t q0, size_t npairs, const uint64_t *ids, const int32_t *counts, const int32_t *proper,
                      const SamAlignments &aln, const int32_t *mapq = nullptr, const SamContigs *ctg = nullptr,
-                     const std::vector<std::string> *quals = nullptr);
+                     const std::vector<std::string> *quals = nullptr, const SamXa *xa = nullptr);
 
 // Mate rescue (include/drm_hip.h, drm_mate_rescue): the region of one anchor id, the one statement of the rule that
 // the host entry points (formats.cpp) and the kernel (mate_rescue.hip) both compile. dlo / dhi are

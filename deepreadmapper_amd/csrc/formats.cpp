@@ -603,12 +603,42 @@ static void append_md_tag(std::string &buf, const drm::SamAlignments &aln, size_
     buf += "\tMD:Z:" + md;
 }
 
+// DRM_SAM_LOCI: "\tXA:Z:" and one "RNAME,<+|->POS,CIGAR,NM;" per alternate of block row `read` that holds an
+// alignment; empty when none does (drm_internal.h, SamXa)
+static std::string xa_tag(const drm::SamXa &xa, size_t read, const std::string &tagged, const std::string &ref_name,
+                          size_t ref_len)
+{
+    const int pre = !tagged.empty() && tagged.front() == '<', post = tagged.size() > 1 && tagged.back() == '>';
+    const drm::SamAlignments &aln = *xa.aln;
+    std::string tag, cigar;
+    for (size_t j = xa.first; j < xa.width && (int64_t)j < (int64_t)xa.counts[read]; ++j) {
+        const size_t row = read * xa.width + j;
+        const drm_sw_alignment &a = aln.rec[row];
+        if (a.status == 1)
+            continue;
+        const uint64_t sid = xa.ids[row];
+        const bool rev = (sid & 1u) != 0;
+        int64_t pos1 = 0;
+        if (aln.region_start)
+            sam_cigar(a, aln.ops + aln.ops_off[row], (int32_t)tagged.size(), pre, post, aln.region_start[row],
+                      aln.region_len[row], rev, pos1, cigar);
+        else
+            sam_cigar(a, aln.ops + aln.ops_off[row], (int32_t)tagged.size(), pre, post, (int64_t)(sid / 2),
+                      (int32_t)ref_len, rev, pos1, cigar);
+        const drm::FastaContig *c = xa.ctg ? &(*xa.ctg->table)[(size_t)xa.ctg->row_contig[row]] : nullptr;
+        tag += tag.empty() ? "\tXA:Z:" : "";
+        tag += (c ? c->name : ref_name) + "," + (rev ? "-" : "+") + std::to_string(pos1 - (c ? c->start : 0)) + "," +
+               cigar + "," + std::to_string(a.nm) + ";";
+    }
+    return tag;
+}
+
 // one row of the DRM_SAM_CIGAR mode: real POS / CIGAR, SEQ on the forward strand, AS and NM; a hit without an
-// alignment is written as unmapped
+// alignment is written as unmapped. `tail` (the XA:Z tag) comes last on a mapped line.
 static void append_aligned_row(std::string &buf, const std::string &qname, int flag, const std::string &ref_name,
                                size_t ref_len, const std::string &tagged, uint64_t sid,
                                const drm::SamAlignments &aln, size_t row, const int32_t *mapq, int64_t contig_start = 0,
-                               const std::string *qual = nullptr)
+                               const std::string *qual = nullptr, const std::string *tail = nullptr)
 {
     const drm_sw_alignment &a = aln.rec[row];
     // the read is the query without format_fastq's tags (an untagged .txt query is the read itself)
@@ -643,6 +673,8 @@ static void append_aligned_row(std::string &buf, const std::string &qname, int f
         buf += "\tAS:i:" + std::to_string(a.score);
         buf += "\tNM:i:" + std::to_string(a.nm);
         append_md_tag(buf, aln, row, (sid & 1u) != 0);
+        if (tail)
+            buf += *tail;
     }
     buf += '\n';
 }
@@ -664,12 +696,15 @@ void drm::write_sam_block(const std::string &path, bool header, const std::strin
                           const std::vector<std::string> &query_seqs, const std::vector<std::string> &query_ids,
                           size_t q0, size_t nq, const uint64_t *ids, const int32_t *counts, size_t k,
                           const SamAlignments *aln, const int32_t *mapq, const SamContigs *ctg,
-                          const std::vector<std::string> *quals)
+                          const std::vector<std::string> *quals, bool loci, bool xa)
 {
     if (quals && quals->empty())
         quals = nullptr;
     if (ctg && !aln)
         throw Error(DRM_ERR_ARG, "a contig table needs the rows' alignments");
+    if ((loci && !aln) || (xa && !loci))
+        throw Error(DRM_ERR_ARG, "lines per locus need the rows' alignments, and XA the lines per locus");
+    const SamXa alternates{ids, counts, k, 1, aln, ctg};
     std::ofstream out(path, header ? std::ios::out : std::ios::app);
     if (!out.is_open())
         throw Error(DRM_ERR_IO, "Failed to open SAM file: " + path);
@@ -686,7 +721,10 @@ void drm::write_sam_block(const std::string &path, bool header, const std::strin
         const std::string cigar = std::to_string(clean.size()) + "M";
         const std::string *qual = quals ? &(*quals)[g] : nullptr;
         const std::string qual_col = qual && !qual->empty() ? *qual : std::string("*");
-        for (int j = 0; j < counts[i] && (size_t)j < k; ++j) {
+        // DRM_SAM_XA: the rows behind the primary go into its XA:Z tag
+        const std::string tail = xa && counts[i] > 1 ? xa_tag(alternates, i, query_seqs[g], ref_name, ref_len)
+                                                     : std::string();
+        for (int j = 0; j < (xa ? std::min(counts[i], 1) : counts[i]) && (size_t)j < k; ++j) {
             const uint64_t sid = ids[i * k + (size_t)j];
             int flag = j == 0 ? 0 : 256; // primary / secondary
             if (sid % 2 == 1)
@@ -694,12 +732,12 @@ void drm::write_sam_block(const std::string &path, bool header, const std::strin
             if (ctg) {
                 const FastaContig &c = (*ctg->table)[(size_t)ctg->row_contig[i * k + (size_t)j]];
                 append_aligned_row(buf, qname, flag, c.name, ref_len, query_seqs[g], sid, *aln, i * k + (size_t)j, mapq,
-                                   c.start, qual);
+                                   c.start, qual, &tail);
                 continue;
             }
             if (aln) {
                 append_aligned_row(buf, qname, flag, ref_name, ref_len, query_seqs[g], sid, *aln, i * k + (size_t)j,
-                                   mapq, 0, qual);
+                                   mapq, 0, qual, &tail);
                 continue;
             }
             buf += qname;
@@ -719,7 +757,8 @@ void drm::write_sam_block(const std::string &path, bool header, const std::strin
             buf += qual_col;
             buf += '\n';
         }
-        if (ctg && counts[i] < 1) // DRM_CONTIGS: a read without a row inside a contig is written unmapped
+        // DRM_CONTIGS: a read without a row inside a contig is written unmapped; DRM_SAM_LOCI: a read without a locus
+        if ((ctg || loci) && counts[i] < 1)
             buf += qname + "\t4\t*\t0\t0\t*\t*\t0\t0\t" + (clean.empty() ? std::string("*") : clean) + "\t" + qual_col +
                    "\n";
         if (buf.size() > (1u << 22)) {
@@ -1105,7 +1144,7 @@ void drm::write_sam_pairs(const std::string &path, bool header, const std::strin
                           const std::vector<std::string> &query_seqs, const std::vector<std::string> &query_ids,
                           size_t q0, size_t npairs, const uint64_t *ids, const int32_t *counts, const int32_t *proper,
                           const SamAlignments &aln, const int32_t *mapq, const SamContigs *ctg,
-                          const std::vector<std::string> *quals)
+                          const std::vector<std::string> *quals, const SamXa *xa)
 {
     if (quals && quals->empty())
         quals = nullptr;
@@ -1187,6 +1226,8 @@ void drm::write_sam_pairs(const std::string &path, bool header, const std::strin
                 buf += "\tAS:i:" + std::to_string(aln.rec[2 * p + (size_t)m].score);
                 buf += "\tNM:i:" + std::to_string(aln.rec[2 * p + (size_t)m].nm);
                 append_md_tag(buf, aln, 2 * p + (size_t)m, in[m].reverse != 0);
+                if (xa) // DRM_SAM_LOCI: the mate's other loci
+                    buf += xa_tag(*xa, 2 * p + (size_t)m, query_seqs[q0 + 2 * p + (size_t)m], ref_name, ref_len);
             }
             buf += '\n';
         }

@@ -683,6 +683,48 @@ int drm_pair_mapq_rescued(const drm_mapq_params *mp, const drm_pair_result *pair
                           const int32_t *full1, const int32_t *full2, int64_t npairs, int64_t row_step,
                           drm_pair_mapq_result *inout);
 
+/* ---------------------------------------------------------------- Locus list
+ * The distinct loci of a read's hit list: the placements a SAM writer prints as the primary line and its secondary
+ * lines or XA entries. The reference has no such step, so this text is the definition. The hit model, "same locus",
+ * "top of a set" and the head rule are drm_hit_mapq's, word for word, and so are the lists, counts, heads, self
+ * scores, their argument ranges and the host form's score check. New parameters: 1 <= max_loci <= 64 (0 or less:
+ * DRM_ERR_ARG; beyond 64: DRM_ERR_UNSUPPORTED) and 0 <= drop_pct <= 100 (DRM_ERR_ARG outside).
+ * With head row h (h = -1: the list's top hit) the enumeration of one list runs as follows:
+ *   1. There is no head (h = -1 with no live row, or a given h that is not a live counted row): the MAPQ record is the
+ *      "nothing" record (status 1), n_loci = n_pass = 0 and every slot is empty.
+ *   2. Locus 0 = every live row in the same locus as h. It is always recorded, in slot 0, with id(h), s(h), row h and
+ *      size = its number of rows, and it counts in n_pass. best_score = s(h). Locus 0 is removed.
+ *   3. Repeat with t = the top of what remains and s = s(t); stop when nothing remains.
+ *        counts_sub = s >= sub_score - sub_band, sub_score being s of the first t, as in drm_hit_mapq;
+ *        passes     = s >= min_score and 100 * s >= drop_pct * best_score.
+ *      Neither holds: stop. counts_sub: n_sub += 1. passes: n_pass += 1, and if n_loci < max_loci the locus is recorded
+ *      in the next slot as (id(t), s, row t, size = the rows removed in this step). Then every remaining row in the
+ *      same locus as t is removed.
+ *      The tops come in non-increasing score, so both tests are monotone and n_sub equals drm_hit_mapq's.
+ * Example: rows at positions 0, 100, 200 of one strand with scores 100, 90, 80, a span of 150, min_score 39 and
+ * drop_pct 80 give slot 0 = {row 0, score 100, size 2} and slot 1 = {row 2, score 80, size 1}; with drop_pct 81 the
+ * second locus no longer passes, and n_loci = n_pass = 1.
+ * Outputs per read r: out[r], byte for byte drm_hit_mapq's record for the same list, head, full and parameters;
+ * n_loci[r], the slots recorded; n_pass[r], the loci that pass in the whole list (n_pass > n_loci: the list was
+ * truncated at max_loci); and slot j of the read at index r * max_loci + j of loci_ids (u64), loci_scores, loci_rows
+ * and loci_size (i32). A slot at or beyond n_loci[r] holds id ~0, score 0, row -1, size 0, so every byte of the
+ * outputs is defined. loci_ids / loci_scores / n_loci have the rerank's layout (ids[r * width + j], cnt[r]) with
+ * width = max_loci: drm_sw_align*, drm_sw_align_md and a SAM writer consume them unchanged. nreads == 0 is DRM_OK and
+ * touches nothing. */
+typedef struct {
+    int32_t max_loci, drop_pct;
+} drm_loci_params;
+int drm_hit_loci(const drm_mapq_params *mp, const drm_loci_params *lp, const uint64_t *ids, const int32_t *scores,
+                 const int32_t *cnt, const int32_t *head, const int32_t *full, int64_t nreads, int32_t k,
+                 drm_mapq_result *out, int32_t *n_loci, int32_t *n_pass, uint64_t *loci_ids, int32_t *loci_scores,
+                 int32_t *loci_rows, int32_t *loci_size);
+/* Device-buffer form, enqueued on `stream`. Stateless: no handle, the current device. */
+int drm_hit_loci_device(const drm_mapq_params *mp, const drm_loci_params *lp, const uint64_t *d_ids,
+                        const int32_t *d_scores, const int32_t *d_cnt, const int32_t *d_head, const int32_t *d_full,
+                        int64_t nreads, int32_t k, drm_mapq_result *d_out, int32_t *d_n_loci, int32_t *d_n_pass,
+                        uint64_t *d_loci_ids, int32_t *d_loci_scores, int32_t *d_loci_rows, int32_t *d_loci_size,
+                        void *stream);
+
 /* ---------------------------------------------------------------- Template-length window from the reads
  * drm_pair_hits, drm_mate_rescue and drm_pair_mapq all take the window [min_tlen, max_tlen] a proper pair's template
  * length must lie in. It is a property of the sequenced library, so it is estimated from the batch being mapped, as

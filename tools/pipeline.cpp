@@ -33,6 +33,14 @@
 // the contig's name in RNAME and positions that count from the contig's start.
 // DRM_SAM_MD=1 (with DRM_SAM_CIGAR=1) appends MD:Z:<string> behind NM:i on every mapped line: a GPU pass over the rows'
 // records and operation words (drm_sw_align_md), then drm_sam_md on the writer thread.
+// DRM_SAM_LOCI=n (1..64, with DRM_SAM_MAPQ=1 and all it needs) prints one line per distinct locus of a read instead of
+// one per rerank row: drm_hit_loci replaces the block's drm_hit_mapq and lists up to n loci that score at least
+// DRM_MAPQ_MIN and DRM_LOCI_DROP=pct (default 80) per cent of the primary; only their head rows are aligned; slot 0 is
+// the primary line, the others secondary lines (flag 256, MAPQ 0); a read without a locus at or above DRM_MAPQ_MIN is
+// written once, unmapped (flag 4). DRM_SAM_XA=1 beside it folds the alternatives into XA:Z:RNAME,<+|->POS,CIGAR,NM;...
+// at the end of the primary line. With DRM_MATES the alternatives of every mate whose line comes from a list row are
+// aligned in a second pass and appended as XA:Z; nothing else on a paired line changes.
+// DRM_SAM_STATS=1 prints the SAM stage's time and the rows it aligned.
 // DRM_SAM_QUAL=1 keeps the quality lines of .fastq / .fq queries (and DRM_MATES) and prints them in column 11, reversed
 // on a line whose SEQ is reverse-complemented; a quality line of another length than its read ends the run.
 // Sequence inputs are embedded by the reference's GRU model on the GPU (drm_vectorize) when
@@ -446,6 +454,31 @@ static bool mapq_mode_from_env(size_t ref_len, bool l2_rows, drm_mapq_params &pr
     return true;
 }
 
+// DRM_SAM_LOCI=n (1..64, with DRM_SAM_MAPQ=1 and everything that needs): one SAM line per distinct locus of a read
+// instead of one per rerank row, from drm_hit_loci with max_loci = n. DRM_LOCI_DROP=pct (default 80, bwa-mem's XA drop
+// ratio: a default, not a measurement) is read only then. DRM_SAM_XA=1 beside it folds the alternative loci into an
+// XA:Z tag on the primary line; pairs always take that form. All three are parsed as strictly as DRM_SAM_SCORING.
+constexpr int32_t kLociDropDefault = 80;
+static bool loci_mode_from_env(bool mapq, drm_loci_params &prm, bool &xa)
+{
+    const char *e = std::getenv("DRM_SAM_LOCI"), *x = std::getenv("DRM_SAM_XA");
+    long n = 0, drop = kLociDropDefault, flag = 0;
+    env_range("DRM_SAM_XA", 0, 1, flag);
+    xa = flag != 0;
+    if (!e) {
+        if (xa)
+            throw drm::Error(DRM_ERR_ARG, "DRM_SAM_XA needs DRM_SAM_LOCI=n: the tag lists the loci it finds: " + quoted(x));
+        return false;
+    }
+    env_range("DRM_SAM_LOCI", 1, 64, n);
+    env_range("DRM_LOCI_DROP", 0, 100, drop);
+    if (!mapq)
+        throw drm::Error(DRM_ERR_ARG, "DRM_SAM_LOCI needs DRM_SAM_MAPQ=1 (with use_dynamic=1 use_streaming=1 "
+                                      "DRM_SAM_CIGAR=1 and sequence queries): the loci come from the MAPQ's scan");
+    prm = drm_loci_params{(int32_t)n, (int32_t)drop};
+    return true;
+}
+
 // What one run does, from argv and every DRM_* variable this file reads; nothing after read_options calls getenv.
 struct Options {
     std::string query_file, ref_file, out_dir, sam_file;
@@ -459,12 +492,15 @@ struct Options {
     AffineMode affine_mode{};
     PairMode pair{};
     drm_mapq_params mapq_prm{};
+    bool loci = false, sam_xa = false; // DRM_SAM_LOCI: lines per locus (drm_hit_loci); DRM_SAM_XA: alternates as XA:Z
+    drm_loci_params loci_prm{};
     std::vector<int> devices;
     // the output mode: the first that holds of header_only, l2_rows, paired, stream_sam; none = the .npy files
     bool stream_sam = false, header_only = false, l2_rows = false;
     bool sam_from_search = false, sam_cigar = false, l2_rows_from_sw = false;
     bool sam_md = false;   // DRM_SAM_MD: MD:Z behind NM:i on every mapped line of the DRM_SAM_CIGAR modes
     bool sam_qual = false; // DRM_SAM_QUAL: column 11 from the FASTQ's quality lines
+    bool sam_stats = false; // DRM_SAM_STATS: one line with the SAM stage's time and the rows it aligned
     size_t sam_block = 0; // DRM_SAM_BLOCK, 0 = unset
 
     const AffineMode *affine() const { return has_affine ? &affine_mode : nullptr; }
@@ -523,6 +559,7 @@ static Options read_options(int argc, char *argv[], size_t ref_len, size_t strid
         throw drm::Error(DRM_ERR_UNSUPPORTED, "DRM_MATES runs on one device (DRM_DEVICE), not on DRM_DEVICES");
     if (o.mapq && o.devices.size() != 1)
         throw drm::Error(DRM_ERR_UNSUPPORTED, "DRM_SAM_MAPQ runs on one device (DRM_DEVICE), not on DRM_DEVICES");
+    o.loci = loci_mode_from_env(o.mapq, o.loci_prm, o.sam_xa);
     // DRM_CONTIGS=1: everything it needs is checked here, before the index is loaded
     o.contigs = env_flag("DRM_CONTIGS");
     if (o.contigs) {
@@ -548,6 +585,7 @@ static Options read_options(int argc, char *argv[], size_t ref_len, size_t strid
     if (o.sam_md && !cigar)
         throw drm::Error(DRM_ERR_ARG, "DRM_SAM_MD needs DRM_SAM_CIGAR=1: MD describes a real alignment");
     o.sam_qual = env_flag("DRM_SAM_QUAL");
+    o.sam_stats = env_flag("DRM_SAM_STATS");
     if (const char *e = std::getenv("DRM_SAM_BLOCK"))
         o.sam_block = std::max<size_t>(1, std::strtoull(e, nullptr, 10));
     if (!o.is_npy)
@@ -659,6 +697,10 @@ struct Pipeline {
     std::vector<uint64_t> spread;
     std::vector<int32_t> row_contig;
     drm_pair_params pair_prm; // o.pair.prm, with DRM_PAIR_TLEN=auto the estimated window from estimate_tlen on
+    // DRM_SAM_STATS: the rows handed to the aligner and the time of the blocks' produce steps (everything between the
+    // rerank and the writer thread: the locus scans, the alignments, the MD pass)
+    size_t aligned_rows = 0;
+    double produce_ms = 0;
 
     explicit Pipeline(const Options &opt)
         : o(opt), k((size_t)opt.k), kc((size_t)opt.k_clusters), device(opt.devices[0]), pair_prm(opt.pair.prm)
@@ -877,9 +919,11 @@ struct Pipeline {
 
     // contig: with DRM_CONTIGS the contig of every row, indexed like ids (the flank guard)
     void align_block(BlockAlignments &ba, const uint64_t *ids, const int32_t *cnt, size_t lo, size_t m, size_t width,
-                     const int32_t *contig = nullptr)
+                     const int32_t *contig = nullptr, bool md = true)
     {
-        ba.want_md = o.sam_md;
+        ba.want_md = o.sam_md && md;
+        for (size_t i = 0; i < m; ++i)
+            aligned_rows += (size_t)std::clamp<int64_t>(cnt[i], 0, (int64_t)width);
         ba.align(art, ids, cnt, m, width, qbuf.p + lo * qs, ql.p + lo, (int32_t)qs, (int32_t)o.ref_len, o.affine(),
                  contig ? ctg : nullptr, contig);
     }
@@ -972,7 +1016,9 @@ struct Pipeline {
                 try {
                     if (o.contigs)
                         contig_stage(lo * per, m * per);
+                    const auto tp = clk::now();
                     write = produce(lo, m);
+                    produce_ms += std::chrono::duration<double, std::milli>(clk::now() - tp).count();
                 } catch (...) {
                     join();
                     throw;
@@ -1220,11 +1266,103 @@ struct Pipeline {
             }
         }
         align_block(*ba, ids->data(), cnt->data(), lo, m, 1, o.contigs ? contig->data() : nullptr);
-        return [this, lo, mp, ids, cnt, proper, ba, line_mapq, contig] {
-            const drm::SamContigs sc{&ctable, contig->data()};
+        // DRM_SAM_LOCI: the loci of every list whose chosen row j_m became the mate's line (not a rescued or unmapped
+        // mate), head = j_m; the alternates, slots 1 .., are aligned in a pass of their own and printed as XA:Z
+        const size_t na = o.loci ? (size_t)o.loci_prm.max_loci - 1 : 0;
+        auto xa_ids = std::make_shared<std::vector<uint64_t>>(m * na, 0);
+        auto xa_cnt = std::make_shared<std::vector<int32_t>>(na ? m : 0, 0);
+        auto xa_contig = std::make_shared<std::vector<int32_t>>(o.contigs ? m * na : 0, -1);
+        auto xa_ba = std::make_shared<BlockAlignments>();
+        if (na) {
+            std::vector<int32_t> head(m, -2); // -2: no row of the list, the "nothing" record
+            for (size_t p = 0; p < mp; ++p) {
+                const int32_t st = after[p].status;
+                if (res[p].j1 >= 0 && st != 6)
+                    head[2 * p] = res[p].j1;
+                if (res[p].j2 >= 0 && st != 5)
+                    head[2 * p + 1] = res[p].j2;
+            }
+            const BlockLoci b = hit_loci(lo, m, head);
+            for (size_t r = 0; r < m; ++r)
+                for (size_t j = 1; j < (size_t)b.n_loci[r]; ++j) {
+                    const size_t row = (lo + r) * k + (size_t)b.rows[r * b.n + j];
+                    (*xa_ids)[r * na + j - 1] = sw_ids.p[row];
+                    if (o.contigs)
+                        (*xa_contig)[r * na + j - 1] = row_contig[row];
+                    (*xa_cnt)[r] = (int32_t)j;
+                }
+            align_block(*xa_ba, xa_ids->data(), xa_cnt->data(), lo, m, na, o.contigs ? xa_contig->data() : nullptr, false);
+        }
+        return [this, lo, mp, ids, cnt, proper, ba, line_mapq, contig, na, xa_ids, xa_cnt, xa_contig, xa_ba] {
+            const drm::SamContigs sc{&ctable, contig->data()}, xsc{&ctable, xa_contig->data()};
+            const drm::SamAlignments xav = xa_ba->view();
+            const drm::SamXa xa{xa_ids->data(), xa_cnt->data(), na, 0, &xav, o.contigs ? &xsc : nullptr};
             drm::write_sam_pairs(o.sam_file, lo == 0, "ref", o.ref_len, qseqs, qids, lo, mp, ids->data(), cnt->data(),
                                  proper->data(), ba->view(), o.mapq ? line_mapq->data() : nullptr,
-                                 o.contigs ? &sc : nullptr, &quals);
+                                 o.contigs ? &sc : nullptr, &quals, na ? &xa : nullptr);
+        };
+    }
+
+    // DRM_SAM_LOCI: drm_hit_loci over the rerank rows of reads [lo, lo + m) with the given head rows, on the spread ids
+    // under DRM_CONTIGS; a slot's real id and contig are those of its row (loci_rows) in the rerank's arrays
+    struct BlockLoci {
+        size_t n = 0; // slots per read
+        std::vector<drm_mapq_result> rec;
+        std::vector<int32_t> n_loci, n_pass, scores, rows, size;
+        std::vector<uint64_t> ids;
+    };
+    BlockLoci hit_loci(size_t lo, size_t m, const std::vector<int32_t> &head)
+    {
+        BlockLoci b;
+        b.n = (size_t)o.loci_prm.max_loci;
+        b.rec.resize(m);
+        b.n_loci.resize(m);
+        b.n_pass.resize(m);
+        b.ids.resize(m * b.n);
+        b.scores.resize(m * b.n);
+        b.rows.resize(m * b.n);
+        b.size.resize(m * b.n);
+        std::vector<int32_t> full(m);
+        for (size_t i = 0; i < m; ++i)
+            full[i] = untagged_length(qseqs[lo + i]);
+        check(drm_set_device(device));
+        check(drm_hit_loci(&o.mapq_prm, &o.loci_prm, level_ids() + lo * k, sw_scores.p + lo * k, status.p + lo,
+                           head.data(), full.data(), (int64_t)m, o.k, b.rec.data(), b.n_loci.data(), b.n_pass.data(),
+                           b.ids.data(), b.scores.data(), b.rows.data(), b.size.data()));
+        return b;
+    }
+
+    // DRM_SAM_LOCI, single reads: one drm_hit_loci per block with head = row 0 (the primary, as DRM_SAM_MAPQ has it),
+    // the alignment of only the recorded loci's head rows (width n), and per read its primary line from slot 0 and a
+    // secondary line -- or with DRM_SAM_XA an XA:Z entry -- per further slot. A read without a head, or whose best
+    // score is below min_score, keeps no row and is written unmapped.
+    std::function<void()> produce_loci(size_t lo, size_t m)
+    {
+        const BlockLoci b = hit_loci(lo, m, std::vector<int32_t>(m, 0));
+        const size_t n = b.n;
+        auto ids = std::make_shared<std::vector<uint64_t>>(m * n, 0);
+        auto cnt = std::make_shared<std::vector<int32_t>>(m, 0);
+        auto contig = std::make_shared<std::vector<int32_t>>(o.contigs ? m * n : 0, -1);
+        auto line_mapq = std::make_shared<std::vector<int32_t>>(m * n, 0); // secondary lines print 0
+        auto ba = std::make_shared<BlockAlignments>();
+        for (size_t i = 0; i < m; ++i) {
+            if (b.rec[i].status != 0 || b.rec[i].best_score < o.mapq_prm.min_score)
+                continue;
+            (*cnt)[i] = b.n_loci[i];
+            (*line_mapq)[i * n] = b.rec[i].mapq;
+            for (size_t j = 0; j < (size_t)b.n_loci[i]; ++j) {
+                const size_t row = (lo + i) * k + (size_t)b.rows[i * n + j];
+                (*ids)[i * n + j] = sw_ids.p[row];
+                if (o.contigs)
+                    (*contig)[i * n + j] = row_contig[row];
+            }
+        }
+        align_block(*ba, ids->data(), cnt->data(), lo, m, n, o.contigs ? contig->data() : nullptr);
+        return [this, lo, m, n, ids, cnt, contig, ba, line_mapq] {
+            const drm::SamAlignments av = ba->view();
+            const drm::SamContigs sc{&ctable, contig->data()};
+            drm::write_sam_block(o.sam_file, lo == 0, "ref", o.ref_len, qseqs, qids, lo, m, ids->data(), cnt->data(), n,
+                                 &av, line_mapq->data(), o.contigs ? &sc : nullptr, &quals, true, o.sam_xa);
         };
     }
 
@@ -1233,6 +1371,8 @@ struct Pipeline {
     // src/utils/utils.cpp:409-503)
     std::function<void()> produce_reads(size_t lo, size_t m)
     {
+        if (o.loci)
+            return produce_loci(lo, m);
         const bool from_search = o.sam_from_search;
         const size_t kr = from_search ? kc : k;
         const uint64_t *rows = from_search ? reinterpret_cast<const uint64_t *>(I.p) + lo * kc : sw_ids.p + lo * k;
@@ -1284,11 +1424,18 @@ struct Pipeline {
         if (o.paired && o.pair.tlen_auto)
             estimate_tlen();
         open_sam(o.paired ? " (paired)" : "");
-        if (o.paired) // DRM_SAM_BLOCK counts pairs here; the file does not depend on it
-            return stream_blocks(nq / 2, 2, o.block(2), [&](size_t p0, size_t mp) { return produce_pairs(p0, mp); });
-        // blocks of DRM_SAM_BLOCK queries; the file does not depend on it
-        return stream_blocks(nq, 1, o.block(o.sam_from_search ? (size_t)std::min(o.k, o.k_clusters) : k),
-                             [&](size_t lo, size_t m) { return produce_reads(lo, m); });
+        const auto t0 = clk::now();
+        const int rc =
+            o.paired // DRM_SAM_BLOCK counts pairs here; the file does not depend on it
+                ? stream_blocks(nq / 2, 2, o.block(2), [&](size_t p0, size_t mp) { return produce_pairs(p0, mp); })
+                // blocks of DRM_SAM_BLOCK queries; the file does not depend on it
+                : stream_blocks(nq, 1, o.block(o.sam_from_search ? (size_t)std::min(o.k, o.k_clusters) : k),
+                                [&](size_t lo, size_t m) { return produce_reads(lo, m); });
+        if (o.sam_stats)
+            std::cout << "[MAIN] SAM stage: " << produce_ms << " ms between the rerank and the writer, " << aligned_rows
+                      << " rows aligned, " << std::chrono::duration<double, std::milli>(clk::now() - t0).count()
+                      << " ms for the block loop" << std::endl;
+        return rc;
     }
 
     // save_results (src/utils/utils.cpp:264-334)
