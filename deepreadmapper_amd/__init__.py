@@ -9,7 +9,8 @@ from .rerank import (WindowTable, calc_sw_score, calc_sw_scores, post_process_sw
                      rerank_arrays, sw_reranker, GenomeTable, extract_fasta_sequence, post_process_sw_dynamic,
                      rerank_dynamic_arrays, embed_windows, l2_rerank_arrays, post_process_l2_static,
                      l2_rerank_dynamic_arrays, post_process_l2_dynamic, sw_align_arrays, sam_cigar,
-                     SW_ALIGNMENT_DTYPE, sw_align_affine_arrays, sw_align_region, sam_cigar_region,
+                     SW_ALIGNMENT_DTYPE, sw_align_affine_arrays, sw_align_affine_clip_arrays, sw_align_region,
+                     sam_cigar_region,
                      SW_MD_DTYPE, sw_align_md_arrays, sam_md)
 
 from .pairing import PAIR_RESULT_DTYPE, pair_hits, pair_hits_device, sam_pair_fields  # noqa: F401  (paired-end reads)

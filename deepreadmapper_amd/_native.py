@@ -46,6 +46,7 @@ EXPORTS = [
     "drm_index_set_exact_stats", "drm_index_broadcast", "drm_index_clone", "drm_device_chase_latency", "drm_device_chase_rows",
     "drm_sw_align", "drm_sw_align_device", "drm_sam_cigar",
     "drm_sw_align_affine", "drm_sw_align_affine_device", "drm_sw_align_region", "drm_sam_cigar_region",
+    "drm_sw_align_affine_clip", "drm_sw_align_affine_clip_device",
     "drm_sw_align_md", "drm_sw_align_md_device", "drm_sam_md",
     "drm_exact_search", "drm_exact_search_device", "drm_exact_search_l2", "drm_exact_search_l2_device",
     "drm_flat_exact_search", "drm_exact_set_slice_rows", "drm_exact_query_tile",
@@ -212,6 +213,9 @@ def lib():
         "drm_sam_cigar": (C.c_int, [vp, vp, i32, i32, i32, i32, C.c_uint64, C.POINTER(i64), C.c_char_p, i32]),
         "drm_sw_align_affine": (C.c_int, [vp, vp, i32, vp, vp, i64, vp, vp, i32, i64, vp, vp, i32]),
         "drm_sw_align_affine_device": (C.c_int, [vp, vp, i32, vp, vp, i64, vp, vp, i32, i64, vp, vp, i32, vp]),
+        "drm_sw_align_affine_clip": (C.c_int, [vp, vp, vp, i32, vp, vp, i64, vp, vp, i32, i64, vp, vp, i32]),
+        "drm_sw_align_affine_clip_device": (C.c_int, [vp, vp, vp, i32, vp, vp, i64, vp, vp, i32, i64, vp, vp, i32,
+                                                      vp]),
         "drm_sw_align_region": (C.c_int, [vp, C.c_uint64, i32, C.POINTER(i64), C.POINTER(i32), C.POINTER(i32)]),
         "drm_sam_cigar_region": (C.c_int, [vp, vp, i32, i32, i32, i64, i32, i32, C.POINTER(i64), C.c_char_p, i32]),
         "drm_sw_align_md": (C.c_int, [vp, i32, vp, vp, i64, vp, vp, i32, i64, vp, vp, vp, vp, vp, i32]),

@@ -1856,6 +1856,55 @@ int drm_sw_align_affine(drm_refs *refs, const drm_sw_scoring *scoring, int32_t f
     });
 }
 
+// the end-aware form (drm_sw_align_affine_clip): the same arguments with the kernel's end-aware instantiation chosen
+static drm::AffineAlignArgs make_affine_clip_args(const drm_refs *refs, const drm_sw_scoring *sc, const drm_sw_clip *clip,
+                                                  int32_t flank)
+{
+    drm::AffineAlignArgs aa = make_affine_args(refs, sc, flank);
+    if (!clip)
+        throw Error(DRM_ERR_ARG, "null clip");
+    if (clip->penalty < 0 || clip->penalty > 63 || clip->tag_prefix < 0 || clip->tag_postfix < 0)
+        throw Error(DRM_ERR_ARG, "clip: penalty must be 0..63 and both tags >= 0");
+    aa.end_aware = 1;
+    aa.clip_penalty = clip->penalty;
+    aa.tag_prefix = clip->tag_prefix;
+    aa.tag_postfix = clip->tag_postfix;
+    return aa;
+}
+
+int drm_sw_align_affine_clip_device(drm_refs *refs, const drm_sw_scoring *scoring, const drm_sw_clip *clip,
+                                    int32_t flank, const uint64_t *d_window_ids, const int64_t *d_pair_query,
+                                    int64_t npairs, const uint8_t *d_queries, const int32_t *d_q_len, int32_t q_stride,
+                                    int64_t nq, drm_sw_alignment *d_out, uint32_t *d_ops, int32_t ops_stride,
+                                    void *stream)
+{
+    return guarded([&] {
+        drm::AffineAlignArgs aa = make_affine_clip_args(refs, scoring, clip, flank);
+        aa.base = make_align_args(refs, d_window_ids, d_pair_query, npairs, d_queries, d_q_len, q_stride, nq, d_out,
+                                  d_ops, ops_stride);
+        if (npairs == 0)
+            return;
+        require_list_pointers(d_window_ids, d_pair_query, d_out, nq, d_queries, d_q_len, d_ops, ops_stride);
+        DRM_HIP_CHECK(hipSetDevice(refs->dev.device));
+        drm::launch_sw_align_affine(refs->dev, aa, q_stride, (hipStream_t)stream);
+    });
+}
+
+int drm_sw_align_affine_clip(drm_refs *refs, const drm_sw_scoring *scoring, const drm_sw_clip *clip, int32_t flank,
+                             const uint64_t *window_ids, const int64_t *pair_query, int64_t npairs,
+                             const uint8_t *queries, const int32_t *q_len, int32_t q_stride, int64_t nq,
+                             drm_sw_alignment *out, uint32_t *ops, int32_t ops_stride)
+{
+    return guarded([&] {
+        drm::AffineAlignArgs aa = make_affine_clip_args(refs, scoring, clip, flank);
+        sw_align_host(refs, window_ids, pair_query, npairs, queries, q_len, q_stride, nq, out, ops, ops_stride,
+                      [&](const drm::AlignArgs &a, int max_q) {
+                          aa.base = a;
+                          drm::launch_sw_align_affine(refs->dev, aa, max_q, nullptr);
+                      });
+    });
+}
+
 // ---------------------------------------------------------------------- MD words of aligned pairs (sw_md.hip)
 static drm::MdArgs make_md_args(const drm_refs *refs, int32_t flank, const uint64_t *ids, const int64_t *pq,
                                 int64_t npairs, const uint8_t *q, const int32_t *ql, int32_t q_stride, int64_t nq,

@@ -331,6 +331,9 @@ struct AffineAlignArgs {
     int32_t match, mismatch, gap_open, gap_extend; // the last three are penalties (drm_sw_scoring)
     int32_t flank;
     int32_t dir_lanes; // set by the launch: lanes that hold a query column = direction words per row in LDS
+    // drm_sw_align_affine_clip: end_aware picks the kernel's end-aware instantiation, which alone
+    // reads the other three (drm_sw_clip)
+    int32_t end_aware, clip_penalty, tag_prefix, tag_postfix;
 };
 void launch_sw_align_affine(const DeviceRefs &refs, AffineAlignArgs a, int max_qlen, hipStream_t stream);
 

@@ -12,6 +12,10 @@
 // with H, each in one DPP shift per step. A cell's direction is 4 bits (source of H, "F extended", "E extended"), so a
 // lane writes one 16-bit word per row, [row][lane] over the lanes that hold a query column (102 B per row for 152-byte
 // reads); the traceback runs from LDS in the same kernel.
+//
+// The end-aware instantiation (CLIP, drm_sw_align_affine_clip) is the same loop with the floor of
+// H a per-column register instead of the constant 0 and the end term of the clipping penalty folded into the best-cell
+// key; the plain instantiation compiles to what it was.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,7 +37,7 @@ constexpr int kOpsWords = 2 * kAlignMaxLen; // a walk has at most n + m steps, s
 // LDS: ops[kOpsWords] u32 | region[256] | query[256] | dirs[n][dir_lanes] u16
 constexpr size_t kAffineLdsFixed = sizeof(uint32_t) * kOpsWords + 2 * kAlignMaxLen;
 
-template <int LQ>
+template <int LQ, bool CLIP>
 __global__ __launch_bounds__(64) void sw_align_affine_kernel(AffineAlignArgs aa)
 {
     constexpr int C = LQ / 64;
@@ -48,6 +52,12 @@ __global__ __launch_bounds__(64) void sw_align_affine_kernel(AffineAlignArgs aa)
     const int dir_lanes = aa.dir_lanes; // every query column lies on a lane below it: the launch's ceil(max_qlen / C)
     const int match4 = 4 * aa.match, mismatch4 = 4 * aa.mismatch, ext4 = 4 * aa.gap_extend;
     const int open4 = 4 * (aa.gap_open + aa.gap_extend) - 1; // H - open4 = 4 * (H - open - ext) + 1
+    // CLIP: the read is columns a + 1 .. b (1-based) of the query, b from the pair's own length; an alignment that
+    // starts right of a or ends off b pays clip4 / 4. Keys carry the adjusted score plus kKeyBias, so that the packed
+    // unsigned key stays monotone below 0: adjusted values lie in [-126, 31 * 256].
+    constexpr int kKeyBias = CLIP ? 128 : 0;
+    const int clip4 = CLIP ? 4 * aa.clip_penalty : 0;
+    const int tag_a = CLIP ? aa.tag_prefix : 0;
 
     for (int64_t p = blockIdx.x; p < a.npairs; p += gridDim.x) {
         // ---- the pair's region: the table row, or genome[s, e) around the window, reverse-complemented as a whole for
@@ -75,6 +85,9 @@ __global__ __launch_bounds__(64) void sw_align_affine_kernel(AffineAlignArgs aa)
             m = min(max(a.q_len[qi], 0), min(a.q_stride, LQ));
             qp = a.queries + qi * (int64_t)a.q_stride;
         }
+        const int tag_b = m - (CLIP ? aa.tag_postfix : 0);
+        if (CLIP && tag_b < tag_a) // no read between the tags: no alignment
+            m = 0;
         __syncthreads(); // the previous pair's traceback has read its LDS
         for (int r = lane; r < n; r += 64)
             wbuf[r] = (uint8_t)(rc ? comp_byte(wp[-r]) : (int)wp[r]);
@@ -83,6 +96,7 @@ __global__ __launch_bounds__(64) void sw_align_affine_kernel(AffineAlignArgs aa)
         //      query: it matches no byte, and such columns lie right of every real one, which never reads them. A
         //      padded cell is some real cell's H minus at least its distance from it, so it never reaches the best score.
         int qv[C], H4[C], F4[C];
+        int stop4[C], end4[C]; // CLIP: 4 * floor(j) + 3, and 4 * kKeyBias less the column's end term
         uint32_t cellkey[C];
 #pragma unroll
         for (int c = 0; c < C; ++c) {
@@ -90,15 +104,19 @@ __global__ __launch_bounds__(64) void sw_align_affine_kernel(AffineAlignArgs aa)
             qv[c] = j0 < m ? (int)qp[j0] : -2;
             if (j0 < m)
                 qbuf[j0] = (uint8_t)qv[c];
-            H4[c] = 0;
+            stop4[c] = CLIP && j0 >= tag_a ? (int)kSrcStop - clip4 : (int)kSrcStop; // column j0 + 1 > a
+            end4[c] = 4 * kKeyBias - (j0 + 1 == tag_b ? 0 : clip4);
+            H4[c] = stop4[c] - (int)kSrcStop; // row 0: H = floor(j)
             F4[c] = kNegInf;
             cellkey[c] = (uint32_t)(((63 - lane) << 2) | (3 - c)); // larger = further left
         }
         __syncthreads();
         // the left neighbour's last column: 4 * H of this row and of the row above, 4 * E of this row
-        int left_cur = 0, left_prev = 0, left_e = kNegInf, e_last = kNegInf;
+        // (rows 0 and -1 of the column left of the lane's first: its floor; column 0 is 0 on every row)
+        const int left0 = CLIP && lane * C > tag_a ? -clip4 : 0;
+        int left_cur = left0, left_prev = left0, left_e = kNegInf, e_last = kNegInf;
         // best cell as one key, H << 17 | (511 - row) << 8 | cellkey: max = (score descending, row ascending,
-        // column ascending); H <= 31 * 256 < 2^13
+        // column ascending); H <= 31 * 256 < 2^13. CLIP: H less the end term plus kKeyBias, still < 2^13
         uint32_t best = 0;
         // the lane of the last real column finishes the last row at step n - 1 + (m - 1) / C
         const int steps = (n > 0 && m > 0) ? n + (m - 1) / C : 0;
@@ -116,11 +134,12 @@ __global__ __launch_bounds__(64) void sw_align_affine_kernel(AffineAlignArgs aa)
                     const int f = fk & ~1;
                     e = ek & ~1;
                     const int km = diag + (wb == qv[c] ? match4 : -mismatch4) + (int)kSrcM;
-                    const uint32_t k = (uint32_t)max(max(max(km, f + (int)kSrcF), e + (int)kSrcE), (int)kSrcStop);
+                    const uint32_t k = (uint32_t)max(max(max(km, f + (int)kSrcF), e + (int)kSrcE),
+                                                     CLIP ? stop4[c] : (int)kSrcStop);
                     // bit 0 of fk / ek set = opened: "extended" is its complement, at bits 2 and 3
                     dbits |= ((k & 3u) | ((uint32_t)(~fk & 1) << 2) | ((uint32_t)(~ek & 1) << 3)) << (4 * c);
                     const uint32_t h4 = k & ~3u;
-                    rowbest = max(rowbest, (h4 << 15) | cellkey[c]);
+                    rowbest = max(rowbest, ((CLIP ? h4 + (uint32_t)end4[c] : h4) << 15) | cellkey[c]);
                     diag = up;
                     left = (int)h4;
                     H4[c] = (int)h4;
@@ -144,7 +163,8 @@ __global__ __launch_bounds__(64) void sw_align_affine_kernel(AffineAlignArgs aa)
 
         // ---- traceback: every lane walks the same path (LDS broadcasts), so no lane-0 branch surrounds the loop.
         //      state 0 = H, 1 = F (a run of region bytes, D), 2 = E (a run of query bytes, I)
-        const int score = (int)(best >> 17);
+        const int adj = (int)(best >> 17) - kKeyBias; // the plain score; CLIP: less the end term (no cell: -128)
+        int score = CLIP ? max(adj, 0) : adj;
         const int i_end = score > 0 ? 511 - (int)((best >> 8) & 511u) : 0;
         const int j_end = score > 0 ? (63 - (int)((best >> 2) & 63u)) * C + (3 - (int)(best & 3u)) + 1 : 0;
         int i = i_end, j = j_end, nops = 0, nm = 0, state = 0;
@@ -191,6 +211,8 @@ __global__ __launch_bounds__(64) void sw_align_affine_kernel(AffineAlignArgs aa)
         const int nstore = min(nops, a.ops_stride);
         for (int x = lane; x < nstore; x += 64)
             a.ops[p * (int64_t)a.ops_stride + x] = opsbuf[nops - 1 - x];
+        if (CLIP && score > 0) // the plain affine score of the walk: what it paid for its two ends comes back
+            score += (j > tag_a ? clip4 / 4 : 0) + (j_end != tag_b ? clip4 / 4 : 0);
         if (lane == 0) {
             drm_sw_alignment r;
             r.score = score;
@@ -232,10 +254,9 @@ void launch_sw_align_affine(const DeviceRefs &refs, AffineAlignArgs aa, int max_
     const size_t lds = kAffineLdsFixed + (size_t)std::max(region, 1) * aa.dir_lanes * sizeof(uint16_t);
     const int per_cu = (int)std::min<size_t>(16, (size_t)160 * 1024 / lds) & ~3; // lds <= 34.5 KB: at least 4
     const int grid = (int)std::min<int64_t>(aa.base.npairs, (int64_t)std::max(cus, 1) * per_cu);
-    if (cols == 3)
-        hipLaunchKernelGGL(sw_align_affine_kernel<192>, dim3(grid), dim3(64), lds, stream, aa);
-    else
-        hipLaunchKernelGGL(sw_align_affine_kernel<256>, dim3(grid), dim3(64), lds, stream, aa);
+    auto kernel = cols == 3 ? (aa.end_aware ? sw_align_affine_kernel<192, true> : sw_align_affine_kernel<192, false>)
+                            : (aa.end_aware ? sw_align_affine_kernel<256, true> : sw_align_affine_kernel<256, false>);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, stream, aa);
     DRM_HIP_CHECK(hipGetLastError());
 }
 

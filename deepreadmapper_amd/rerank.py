@@ -340,6 +340,39 @@ def sw_align_affine_arrays(table, window_ids, pair_query, query_seqs, scoring, f
     return _retry_truncated(call, wid, pq, rec, ops, ops_stride, int(qbuf.shape[1]) + int(table.ref_len) + 2 * int(flank))
 
 
+def sw_clip(penalty, tags=(1, 1)):
+    """drm_sw_clip (penalty, tag_prefix, tag_postfix) as the int32 array the C ABI reads."""
+    c = np.array([int(penalty), int(tags[0]), int(tags[1])], dtype=np.int32)
+    if c.shape != (3,):
+        raise ValueError("tags is (tag_prefix, tag_postfix)")
+    return c
+
+
+def sw_align_affine_clip_arrays(table, window_ids, pair_query, query_seqs, scoring, clip, tags=(1, 1), flank=0,
+                                ops_stride=16):
+    """The end-aware affine-gap alignment (drm_sw_align_affine_clip): sw_align_affine_arrays with the clipping
+    penalty `clip` (0..63) that an alignment pays for stopping short of either end of the read, the read being the
+    query without its `tags` = (tag_prefix, tag_postfix) bytes. Records and words are of the same form; `score` is the
+    plain affine score of the printed walk. Pairs with more than ops_stride runs are aligned again, so every returned
+    status is 0 or 1."""
+    wid = np.ascontiguousarray(window_ids, dtype=np.uint64)
+    pq = np.ascontiguousarray(pair_query, dtype=np.int64)
+    if wid.shape != pq.shape or wid.ndim != 1:
+        raise ValueError("window_ids and pair_query must be 1-d arrays of one length")
+    qbuf, qlen = query_seqs if isinstance(query_seqs, tuple) else pack_queries(query_seqs)
+    sc, cl = sw_scoring(scoring), sw_clip(clip, tags)
+
+    def call(w, q, stride):
+        rec = np.zeros(len(w), dtype=SW_ALIGNMENT_DTYPE)
+        ops = np.zeros((len(w), stride), dtype=np.uint32)
+        check(lib().drm_sw_align_affine_clip(table.handle, ptr(sc), ptr(cl), int(flank), ptr(w), ptr(q), len(w),
+                                             ptr(qbuf), ptr(qlen), qbuf.shape[1], len(qlen), ptr(rec),
+                                             ptr(ops) if ops.size else None, int(stride)))
+        return rec, ops
+    rec, ops = call(wid, pq, ops_stride)
+    return _retry_truncated(call, wid, pq, rec, ops, ops_stride, int(qbuf.shape[1]) + int(table.ref_len) + 2 * int(flank))
+
+
 def sw_align_region(table, window_id, flank):
     """(start, length, reverse) of a window id's target region on a GenomeTable (drm_sw_align_region): the bytes
     genome[start : start + length], reverse-complemented when reverse; length 0 for a window past the genome end."""

@@ -386,6 +386,38 @@ int drm_sw_align_affine_device(drm_refs *refs, const drm_sw_scoring *scoring, in
                                const uint64_t *d_window_ids, const int64_t *d_pair_query, int64_t npairs,
                                const uint8_t *d_queries, const int32_t *d_q_len, int32_t q_stride, int64_t nq,
                                drm_sw_alignment *d_out, uint32_t *d_ops, int32_t ops_stride, void *stream);
+/* The clipping penalty (bwa-mem's -L): drm_sw_align_affine made aware of the read's two ends, so that an alignment
+ * which stops short of an end pays a fixed price L and a mismatch a few bases from an end is aligned instead of
+ * soft-clipped. The region, the query bytes (tags included), the raw byte equality, E and F, the record, the operation
+ * words and the status 2 rule are drm_sw_align_affine's. Accepted: penalty 0..63, tag_prefix and tag_postfix >= 0
+ * (DRM_ERR_ARG otherwise). For a pair with query length m let a = tag_prefix and b = m - tag_postfix: the read is
+ * columns a + 1 .. b. A pair with b < a has status 1.
+ *   floor(j) = 0 for j <= a, -L for j > a           (an alignment that starts inside the read has paid L)
+ *   Borders: H[i][0] = 0, H[0][j] = floor(j), E = F = -inf.
+ *   H[i][j] = max(floor(j), H[i-1][j-1] + s, F[i][j], E[i][j]); F and E by the recurrences above over this H.
+ *   adj(i, j) = H[i][j] - (j == b ? 0 : L) for i >= 1, j >= 1   (an alignment that ends off the read's end pays L)
+ *   End cell: the largest adj; among equals the smallest i, then the smallest j. No cell, or a largest adj <= 0, is
+ *   status 1 with every other field 0.
+ * Traceback: the one above, except that state H stops when i == 0, j == 0 or H[i][j] == floor(j), tested before the
+ *   M / F / E conditions: a tie goes to stopping, as it does at 0.
+ * score is the plain affine score of the walk that is printed, adj + L * [q_begin > a] + L * [q_end != b], so that
+ *   replaying the operations under the scoring gives exactly score and AS:i stays comparable between reads.
+ * At L = 0 this is drm_sw_align_affine for any tags, record and words. drm_sam_cigar_region, drm_sw_align_md and
+ * drm_sam_md take the records as they are. */
+typedef struct {
+    int32_t penalty, tag_prefix, tag_postfix;
+} drm_sw_clip;
+/* drm_sw_align_affine's arguments and errors, with the clipping parameters after the scoring. Host pointers. */
+int drm_sw_align_affine_clip(drm_refs *refs, const drm_sw_scoring *scoring, const drm_sw_clip *clip, int32_t flank,
+                             const uint64_t *window_ids, const int64_t *pair_query, int64_t npairs,
+                             const uint8_t *queries, const int32_t *q_len, int32_t q_stride, int64_t nq,
+                             drm_sw_alignment *out, uint32_t *ops, int32_t ops_stride);
+/* Device-buffer form, as drm_sw_align_affine_device. */
+int drm_sw_align_affine_clip_device(drm_refs *refs, const drm_sw_scoring *scoring, const drm_sw_clip *clip,
+                                    int32_t flank, const uint64_t *d_window_ids, const int64_t *d_pair_query,
+                                    int64_t npairs, const uint8_t *d_queries, const int32_t *d_q_len, int32_t q_stride,
+                                    int64_t nq, drm_sw_alignment *d_out, uint32_t *d_ops, int32_t ops_stride,
+                                    void *stream);
 /* Host only: the target region of one window id on a genome handle (DRM_ERR_ARG on a window table or a negative
  * flank, DRM_ERR_UNSUPPORTED when ref_len + 2 * flank > 256): genome[*start, *start + *len), *reverse = 1 when it is
  * reverse-complemented. A window past the genome end has *len = 0 (and *start = 0). */

@@ -14,7 +14,9 @@
 // its dynamic branch, so static + streaming writes no result file there either. DRM_SAM_CIGAR=1 replaces the
 // reference's pseudo POS / CIGAR in that SAM by the GPU alignment of every row (drm_sw_align); with
 // DRM_SAM_SCORING=match,mismatch,open,extend and / or DRM_SAM_FLANK=n beside it, by the affine-gap alignment over the
-// window widened by n genome bases on either side (drm_sw_align_affine).
+// window widened by n genome bases on either side (drm_sw_align_affine). DRM_SAM_CLIP=L (1..63; 0 = off) beside
+// DRM_SAM_CIGAR=1 makes that alignment end-aware (drm_sw_align_affine_clip, bwa-mem's -L): an alignment that stops short
+// of a read end pays L, so a mismatch a few bases from an end is aligned instead of soft-clipped.
 // DRM_MATES=<fastq of second mates> (with use_dynamic=1 use_streaming=1 DRM_SAM_CIGAR=1) maps read pairs: the two files
 // are interleaved, searched and reranked as one batch, drm_pair_hits chooses one hit per mate (DRM_PAIR_TLEN=min,max,
 // DRM_PAIR_PENALTY=n), only those are aligned, and the SAM carries two lines per pair with the pair flags, RNEXT,
@@ -91,10 +93,12 @@ template <class T> struct Pinned {
 // DRM_SAM_CIGAR=1: the GPU alignments (drm_sw_align) of one SAM block's rows, ids[i * k + j] for j < cnt[i] against
 // query lo + i. The first pass keeps 16 operation words per row; the rows that need more (status 2) are aligned
 // again as a sub-list with a stride that cannot overflow. Rows past cnt[i] keep an empty record. With `affine` the
-// rows are aligned by drm_sw_align_affine over their flanked regions, which are kept for the formatter.
+// rows are aligned by drm_sw_align_affine over their flanked regions, which are kept for the formatter; with a clipping
+// penalty by drm_sw_align_affine_clip, the reads being tagged "<" read ">".
 struct AffineMode {
     drm_sw_scoring scoring;
     int32_t flank;
+    int32_t clip; // DRM_SAM_CLIP: 0 = the plain affine alignment
 };
 struct BlockAlignments {
     std::vector<drm_sw_alignment> rec;
@@ -146,7 +150,7 @@ struct BlockAlignments {
                 check(drm_contigs_find(table, start, len, &t));
                 inside[i * k + j] = t >= 0 && t == row_contig[i * k + j];
             }
-        const AffineMode bare{affine->scoring, 0};
+        const AffineMode bare{affine->scoring, 0, affine->clip};
         for (uint8_t &x : inside) // the rows that keep their flank, then the others with none
             x = x ? 1 : 2;
         align_rows(rt, ids, cnt, m, k, queries, q_len, q_stride, ref_len, affine, inside.data(), 1);
@@ -169,8 +173,13 @@ struct BlockAlignments {
                 const int64_t nc = (int64_t)std::min(kChunk, w.size() - c);
                 drm_sw_alignment *rc = r.data() + c;
                 uint32_t *oc = o.data() + c * (size_t)stride;
-                check(affine ? drm_sw_align_affine(rt, &affine->scoring, affine->flank, w.data() + c, q.data() + c, nc,
-                                                   queries, q_len, q_stride, (int64_t)m, rc, oc, stride)
+                const drm_sw_clip clip{affine ? affine->clip : 0, 1, 1};
+                check(affine && affine->clip > 0
+                          ? drm_sw_align_affine_clip(rt, &affine->scoring, &clip, affine->flank, w.data() + c,
+                                                     q.data() + c, nc, queries, q_len, q_stride, (int64_t)m, rc, oc,
+                                                     stride)
+                      : affine ? drm_sw_align_affine(rt, &affine->scoring, affine->flank, w.data() + c, q.data() + c, nc,
+                                                     queries, q_len, q_stride, (int64_t)m, rc, oc, stride)
                              : drm_sw_align(rt, w.data() + c, q.data() + c, nc, queries, q_len, q_stride, (int64_t)m, rc,
                                             oc, stride));
             }
@@ -317,13 +326,18 @@ static void env_int(const char *name, long lo, int32_t &v)
 
 // DRM_SAM_SCORING=match,mismatch,open,extend and DRM_SAM_FLANK=n (with DRM_SAM_CIGAR=1 only): strictly parsed, and
 // checked against drm_sw_align_affine's ranges (drm::check_scoring) before any work. A flank alone means the scoring
-// 1,1,0,1.
+// 1,1,0,1. DRM_SAM_CLIP=L, as strictly: 0..63, drm_sw_clip's range; a penalty above 0 turns the mode on as a flank does,
+// and 0 is the unset variable.
 static bool affine_mode_from_env(size_t ref_len, AffineMode &mode)
 {
     const char *sc = std::getenv("DRM_SAM_SCORING"), *fl = std::getenv("DRM_SAM_FLANK");
-    if (!sc && !fl)
+    const char *cl = std::getenv("DRM_SAM_CLIP");
+    long clip = 0;
+    if (cl && (!parse_int(cl, clip) || clip > 63))
+        throw drm::Error(DRM_ERR_ARG, "DRM_SAM_CLIP must be an integer in [0, 63]: " + quoted(cl));
+    if (!sc && !fl && clip == 0)
         return false;
-    mode = AffineMode{{1, 1, 0, 1}, 0};
+    mode = AffineMode{{1, 1, 0, 1}, 0, (int32_t)clip};
     if (sc) {
         long v[4] = {};
         const long n = parse_int_list(sc, 4, v);

@@ -5,7 +5,10 @@ pairs (one candidate per read, which leaves most of that kernel's lanes idle) an
 is built for (P / 128 reads x 128 candidates). Checks the alignment scores against the rerank's before timing.
 --scoring match,mismatch,open,extend adds the affine kernel (drm_sw_align_affine_device) on the same pairs in the same
 process: at flank 0 on the same window table, and at --flank on a genome handle of the same genome (the same window
-ids). The timed functions take turns run by run, so that a drift of the machine meets all of them alike."""
+ids). --clip L (with --scoring) adds the end-aware kernel (drm_sw_align_affine_clip_device, tags 1 / 1) beside each of
+the two, counts the records it changes and the clipped bases it recovers, and prints its time over the plain affine
+kernel's per run pair. The timed functions take turns run by run, so that a drift of the machine meets all of them
+alike."""
 import argparse
 import statistics
 import sys
@@ -24,7 +27,10 @@ ap.add_argument("--runs", type=int, default=9)
 ap.add_argument("--ops-stride", type=int, default=16)
 ap.add_argument("--scoring", default=None, help="match,mismatch,open,extend: also time the affine kernel")
 ap.add_argument("--flank", type=int, default=8, help="flank of the affine kernel's second timing (genome handle)")
+ap.add_argument("--clip", type=int, default=None, help="clipping penalty: also time the end-aware affine kernel")
 a = ap.parse_args()
+if a.clip is not None and not a.scoring:
+    ap.error("--clip needs --scoring")
 P, K = a.pairs, 128
 
 g = synth.genome(200_000, seed=3)
@@ -69,6 +75,14 @@ def affine(handle, flank):
     return f
 
 
+def affine_clip(handle, flank):
+    def f():
+        check(lib().drm_sw_align_affine_clip_device(handle, scoring.ctypes.data, clip.ctypes.data, flank, d_wid.ptr,
+                                                    d_pq.ptr, P, d_q.ptr, d_ql.ptr, q.shape[1], P, d_rec.ptr, d_ops.ptr,
+                                                    a.ops_stride, st.handle))
+    return f
+
+
 def timed(fs):
     """Median / min / max of --runs runs per function, warm, the functions taking turns."""
     for f in fs:
@@ -83,7 +97,11 @@ def timed(fs):
             e1.record(st)
             st.synchronize()
             ts[x].append(e0.elapsed_ms(e1))
+    times.extend(ts)
     return [(statistics.median(t), min(t), max(t)) for t in ts]
+
+
+times = []  # every run of every timed function, in the order of `jobs`
 
 
 align()
@@ -109,9 +127,33 @@ if a.scoring:
               f"{rec['n_ops'].mean():.2f}, {int((rec['q_end'] - rec['q_begin'] == 150).sum())} of {P} reads aligned "
               f"end to end", flush=True)
         jobs.append((f"sw_align_affine {a.scoring} flank {flank}", affine(handle, flank), P))
+        if a.clip is None:
+            continue
+        clip = np.array([a.clip, 1, 1], dtype=np.int32)
+        plain, plain_ops = rec, d_ops.download()
+        affine_clip(handle, flank)()
+        st.synchronize()
+        rec, ops = d_rec.download(), d_ops.download()
+        assert (rec["status"] == 0).all(), "a read did not align under the clipping penalty"
+        live = np.arange(a.ops_stride)[None, :] < np.maximum(rec["n_ops"], plain["n_ops"])[:, None]  # the rest is stale
+        changed = (rec != plain) | ((ops != plain_ops) & live).any(axis=1)
+        span, span0 = rec["q_end"] - rec["q_begin"], plain["q_end"] - plain["q_begin"]
+        print(f"affine {a.scoring} clip {a.clip} flank {flank}: {int(changed.sum())} of {P} records changed, "
+              f"{int((span - span0).sum())} clipped bases recovered, {int((span == 150).sum())} of {P} reads aligned "
+              f"end to end, mean score {rec['score'].mean():.1f}", flush=True)
+        jobs.append((f"sw_align_affine_clip {a.scoring} clip {a.clip} flank {flank}", affine_clip(handle, flank), P))
 res = timed([f for _, f, _ in jobs])
 for (name, _, n), (med, lo, hi) in zip(jobs, res):
     print(f"{name}: median {med:.3f} ms (min {lo:.3f}, max {hi:.3f}, {a.runs} runs) = {n / med / 1e3:.2f} M pairs/s",
           flush=True)
 if a.scoring:
-    print(f"affine / linear: flank 0 {res[3][0] / res[0][0]:.2f}x, flank {a.flank} {res[4][0] / res[0][0]:.2f}x", flush=True)
+    at = {name: x for x, (name, _, _) in enumerate(jobs)}
+    plain = [at[f"sw_align_affine {a.scoring} flank {flank}"] for flank in (0, a.flank)]
+    print(f"affine / linear: flank 0 {res[plain[0]][0] / res[0][0]:.2f}x, flank {a.flank} "
+          f"{res[plain[1]][0] / res[0][0]:.2f}x", flush=True)
+    if a.clip is not None:
+        for x, flank in zip(plain, (0, a.flank)):  # the end-aware kernel's job follows its plain one
+            ratios = sorted(c / p for c, p in zip(times[x + 1], times[x]))
+            print(f"end-aware / plain affine, flank {flank}: median of medians {res[x + 1][0] / res[x][0]:.3f}x; per "
+                  f"run pair median {statistics.median(ratios):.3f}x (min {ratios[0]:.3f}, max {ratios[-1]:.3f}, "
+                  f"{a.runs} pairs)", flush=True)
