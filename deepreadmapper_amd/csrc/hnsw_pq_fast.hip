@@ -5,8 +5,10 @@
 // restated in oracle/drm_oracle.c). Caller: faiss_search (src/hnswpq/search.cpp:39-40).
 //
 // What makes it lean ("hnsw_pq_fast_kernel"):
-//   * every MinimaxHeap slot is one u64 = (ord32(distance) << 32) | (id ^ 2^31): faiss's cmp2 on
-//     (distance, id) -- popped slots carry id -1 -- becomes a single unsigned 64-bit compare;
+//   * every MinimaxHeap slot is one u64 = (ord32(distance) << 32) | w, w = id | 2^31 for a live slot and w = id
+//     (bit 31 clear) for a popped one: the slot's node id is held once, and "popped" is one bit of the key. faiss's
+//     cmp2 on (distance, id) -- popped slots carry id -1 there -- is a single unsigned 64-bit compare of the keys,
+//     after N(w) = max(w, 2^31 - 1) where both sides can be popped (struct Heap has the argument);
 //   * the heap sits in the sibling-pair layout (lane p holds the children of node p, slots 2p+1 and
 //     2p+2; the root is lane 63's second half); a full-heap replace finds its sift-down path from two
 //     ballots and per-lane ancestor masks, and its sift-up chain by one parallel compare;
@@ -17,8 +19,8 @@
 //     the heap's entries plus the evicted ones that tied with the root they left (a log of those alone);
 //     selected + sorted once per query. k < ef keeps a register result set (k <= 64);
 //   * no visited table. faiss's VisitedTable answers "was this link seen before?"; the kernel answers it
-//     from the heap instead ("The heap is the visited set"). Every heap slot also
-//     carries its node id (IL / IR), popped or not. A link whose distance is at or above the root of the
+//     from the heap instead ("The heap is the visited set"). Every heap slot keeps
+//     its node id in its key's low word, popped or not. A link whose distance is at or above the root of the
 //     full heap is rejected by MinimaxHeap::push whether it was seen or not (the root only falls), and a
 //     seen link below that root has never left the heap; so "seen" == "in the heap" wherever it decides
 //     anything, and the same pushes are accepted in the same order as with faiss's table. The hop's only
@@ -38,8 +40,9 @@
 namespace drm {
 namespace {
 
-constexpr uint32_t kPopLo = 0x7FFFFFFFu;            // low word of a popped slot (id -1 ^ 2^31)
-constexpr uint64_t kUnused = 0xFFFFFFFF7FFFFFFFull; // key above every distance, popped
+constexpr uint32_t kLive = 0x80000000u;             // bit 31 of a key's low word: the slot is live (not popped)
+constexpr uint32_t kPopLo = 0x7FFFFFFFu;            // faiss's low word of a popped slot (id -1 ^ 2^31): N() of every popped w
+constexpr uint64_t kUnused = 0xFFFFFFFF7FFFFFFFull; // key above every distance, popped, no node (no id is 2^31 - 1)
 
 __device__ __forceinline__ uint64_t ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 __device__ __forceinline__ uint64_t pack(uint32_t key, int32_t id)
@@ -49,14 +52,16 @@ __device__ __forceinline__ uint64_t pack(uint32_t key, int32_t id)
 __device__ __forceinline__ uint32_t hi32(uint64_t v) { return (uint32_t)(v >> 32); }
 __device__ __forceinline__ uint32_t lo32(uint64_t v) { return (uint32_t)v; }
 __device__ __forceinline__ int32_t unpack_id(uint64_t v) { return (int32_t)(lo32(v) ^ 0x80000000u); }
-__device__ __forceinline__ int32_t readlane32(int32_t v, int l) { return __builtin_amdgcn_readlane(v, l); }
+// N: the key as faiss orders it -- a popped slot's id is -1 there, so every popped low word becomes kPopLo; a live
+// one (>= 2^31) is unchanged. One 32-bit max (scalar for a wave-uniform key).
+__device__ __forceinline__ uint64_t normk(uint64_t v)
+{
+    const uint32_t lo = lo32(v);
+    return (v & ~0xFFFFFFFFull) | (lo > kPopLo ? lo : kPopLo);
+}
 // llvm.amdgcn.writelane (this clang has no builtin for it): old with lane `lane` (wave-uniform, mod 64) replaced by
 // the wave-uniform val -- one v_writelane_b32, no compare and no copy of val into a VGPR
 extern "C" __device__ int drm_llvm_writelane(int val, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
-__device__ __forceinline__ int32_t writelane32(int32_t v, int32_t s, uint32_t l)
-{
-    return drm_llvm_writelane(s, (int)(l & 63u), v);
-}
 __device__ __forceinline__ uint64_t writelane64(uint64_t v, uint64_t s, uint32_t l)
 {
     const uint32_t h = (uint32_t)drm_llvm_writelane((int)(s >> 32), (int)(l & 63u), (int)(v >> 32));
@@ -77,11 +82,7 @@ __device__ __forceinline__ uint64_t bperm64(uint64_t v, int src)
 {
     return ((uint64_t)bperm32(hi32(v), src) << 32) | bperm32(lo32(v), src);
 }
-__device__ __forceinline__ int32_t bperm32_addr(int32_t v, uint32_t addr) // addr = source lane * 4
-{
-    return __builtin_amdgcn_ds_bpermute((int)addr, v);
-}
-__device__ __forceinline__ uint64_t bperm64_addr(uint64_t v, uint32_t addr)
+__device__ __forceinline__ uint64_t bperm64_addr(uint64_t v, uint32_t addr) // addr = source lane * 4
 {
     return ((uint64_t)(uint32_t)__builtin_amdgcn_ds_bpermute((int)addr, (int)hi32(v)) << 32) |
            (uint32_t)__builtin_amdgcn_ds_bpermute((int)addr, (int)lo32(v));
@@ -189,14 +190,22 @@ struct PathConst {
     }
 };
 
-// MinimaxHeap arrays (ef <= 128) in the sibling-pair layout. L / R are the faiss keys (a popped slot's id is -1
-// there, as in faiss's ids[] array); IL / IR hold each slot's node id, popped or not (-1: never filled), and move
-// with their keys through every sift. They are what the kernel's visited test reads. Lane 63's R / IR is the root.
+// MinimaxHeap arrays (ef <= 128) in the sibling-pair layout. L / R are the slots' keys, (ord32(dist) << 32) | w; lane
+// 63's R is the root. w holds the slot's node id, once: w = id | 2^31 while the slot is live, w = id once pop_min has
+// taken it (bit 31 cleared); a slot never filled holds kUnused (reads as popped; its w, 2^31 - 1, is no node's id). So a
+// slot's node, in the tagged form the links' ids have (id ^ 2^31 = id | 2^31), is w | 2^31, and "valid" is bit 31.
+//
+// faiss's order. faiss's ids[] holds -1 in a popped slot, so its cmp2 sees two popped slots of one distance as equal,
+// where the raw keys would order them by node id. With N(w) = max(w, 2^31 - 1) (normk) a live w is unchanged and
+// every popped w becomes faiss's (-1 ^ 2^31): N(a) > N(b) is cmp2(a, b) exactly. N is applied where both operands
+// can be popped: the children's compare (L > R) and the sifted slot against the chosen child (val > chv), in
+// replace128 and in pop. No other compare needs it: a pushed value is always live, and a live w is above every
+// popped w and above 2^31 - 1 alike, so vnew > L, vnew > R and the father compares of push_fill and push give
+// cmp2's answer on the raw keys. What moves through the heap is always the raw key, never the normalised one.
 struct Heap {
     uint64_t L, R;
-    int32_t IL, IR;
 
-    // value / node id of slot s (wave-uniform s)
+    // value of slot s (wave-uniform s)
     __device__ __forceinline__ uint64_t get(int s) const
     {
         if (s == 0)
@@ -204,31 +213,28 @@ struct Heap {
         const int o = (s - 1) >> 1;
         return (s & 1) ? readlane64(L, o) : readlane64(R, o);
     }
-    __device__ __forceinline__ int32_t get_id(int s) const
+    // node v (tagged) is in the heap, popped or not: each half's w with bit 31 set against v (wave-uniform answer).
+    // The masked compare per test measured faster than two id views (w | 2^31) kept in registers and refreshed by
+    // every push, 83.3 against 83.6 ms at C5 (profiles/r09/ab_bench_heap_ids.txt)
+    __device__ __forceinline__ bool holds(int32_t v) const
     {
-        if (s == 0)
-            return readlane32(IR, 63);
-        const int o = (s - 1) >> 1;
-        return (s & 1) ? readlane32(IL, o) : readlane32(IR, o);
+        return (ballot((lo32(L) | kLive) == (uint32_t)v) | ballot((lo32(R) | kLive) == (uint32_t)v)) != 0ull;
     }
-    // node v is in the heap (one compare per half, wave-uniform answer)
-    __device__ __forceinline__ bool holds(int32_t v) const { return (ballot(IL == v) | ballot(IR == v)) != 0ull; }
-    // the root's key (high word) and node id
+    // the root's key: its high word and its low word w (the root's node, tagged, is w | 2^31)
     __device__ __forceinline__ uint32_t root_hi() const { return (uint32_t)__builtin_amdgcn_readlane((int)hi32(R), 63); }
-    __device__ __forceinline__ int32_t root_id() const { return readlane32(IR, 63); }
+    __device__ __forceinline__ uint32_t root_w() const { return (uint32_t)__builtin_amdgcn_readlane((int)lo32(R), 63); }
 
     // faiss heap_pop<CMax<float, int>>(k): slot k-1 sifted down from the root (1-based k >= 1).
     __device__ __forceinline__ void pop(int k, int lane)
     {
         const uint64_t val = get(k - 1);
-        const int32_t valI = get_id(k - 1);
+        const uint64_t valN = normk(val);
         const bool has_l = 2 * lane + 1 <= k - 1;
         const bool has_r = 2 * lane + 2 <= k - 1 && lane != 63;
-        const bool takeL = !has_r || L > R;                 // (i2 == k + 1) || cmp2(heap[i1], heap[i2])
+        const bool takeL = !has_r || normk(L) > normk(R);   // (i2 == k + 1) || cmp2(heap[i1], heap[i2])
         const int ch = takeL ? 2 * lane + 1 : 2 * lane + 2; // chosen child slot
         const uint64_t chv = takeL ? L : R;
-        const int32_t chI = takeL ? IL : IR;
-        const bool moves = has_l && !(val > chv);           // the child moves up unless cmp2(val, child)
+        const bool moves = has_l && !(valN > normk(chv));   // the child moves up unless cmp2(val, child)
         // next hole position, pointer-doubled: n8(0) is the final hole (depth <= 7)
         const int n1 = moves ? ch : lane;
         int n = n1;
@@ -243,29 +249,20 @@ struct Heap {
         const int sh = bitlen(hx) - bitlen((uint32_t)lane + 1u);
         const bool writer = sh > 0 && (hx >> sh) == (uint32_t)lane + 1u;
         const uint64_t up = bperm64(chv, ch & 63);
-        const int32_t upI = (int32_t)bperm32((uint32_t)chI, ch & 63);
         const bool at_hole = ch == hole;
         const uint64_t nv = at_hole ? val : up;
-        const int32_t nvI = at_hole ? valI : upI;
-        if (writer && takeL) {
+        if (writer && takeL)
             L = nv;
-            IL = nvI;
-        }
-        if (writer && !takeL) {
+        if (writer && !takeL)
             R = nv;
-            IR = nvI;
-        }
         const bool root_moved = hole != 0;
         const uint64_t rootv = root_moved ? readlane64(chv, 0) : val;
-        const int32_t rootI = root_moved ? readlane32(chI, 0) : valI;
-        if (lane == 63) {
+        if (lane == 63)
             R = rootv;
-            IR = rootI;
-        }
     }
 
-    // faiss heap_push<CMax<float, int>>(k, val): val enters at slot k-1 and sifts up (1-based k >= 1).
-    __device__ __forceinline__ void push(int k, uint64_t val, int32_t valI, int lane)
+    // faiss heap_push<CMax<float, int>>(k, val): val (live) enters at slot k-1 and sifts up (1-based k >= 1).
+    __device__ __forceinline__ void push(int k, uint64_t val, int lane)
     {
         // lane j in [1, 7] looks at the ancestor a_j = k >> j (1-based)
         const int aj = (lane >= 1 && lane < 8) ? (k >> lane) : 0;
@@ -273,9 +270,7 @@ struct Heap {
         const int owner = t <= 0 ? 63 : (t - 1) >> 1;
         const bool sideR = t <= 0 || !(t & 1);
         const uint64_t fl = bperm64(L, owner), fr = bperm64(R, owner);
-        const int32_t flI = (int32_t)bperm32((uint32_t)IL, owner), frI = (int32_t)bperm32((uint32_t)IR, owner);
         const uint64_t av = sideR ? fr : fl;
-        const int32_t avI = sideR ? frI : flI;
         const bool moves = aj >= 1 && val > av; // cmp2(val, father): the father moves down
         const int h = __builtin_popcountll(ballot(moves)); // ancestors 1..h move (heap order: a prefix)
         // chain index m (a_m = k >> m, m = 0..h) gets a_{m+1}'s value, or val at m == h
@@ -286,22 +281,14 @@ struct Heap {
         const bool onR = lane != 63 && mr >= 0 && mr <= h && (uint32_t)(k >> mr) == xr;
         const int m = onL ? ml : mr;
         const uint64_t pulled = bperm64(av, (m + 1) & 63);
-        const int32_t pulledI = (int32_t)bperm32((uint32_t)avI, (m + 1) & 63);
         const uint64_t nv = (m == h) ? val : pulled;
-        const int32_t nvI = (m == h) ? valI : pulledI;
-        if (onL) {
+        if (onL)
             L = nv;
-            IL = nvI;
-        }
-        if (onR) {
+        if (onR)
             R = nv;
-            IR = nvI;
-        }
         // the root (lane 63 R, 1-based 1 = a_{bk-1}) changes only if val climbs all the way up
-        if (h == bk - 1 && lane == 63) {
+        if (h == bk - 1 && lane == 63)
             R = val;
-            IR = valI;
-        }
     }
 
     // heap_pop(128) then heap_push(128, vnew) on the full ef = 128 heap (MinimaxHeap::push when k == n), with the
@@ -310,31 +297,29 @@ struct Heap {
     //    with that child's own chosen child (chv of lane ch_p), or with slot 127's value when p is the path's last
     //    node; the path is the set of lanes whose own and ancestors' chosen children move up (PathConst::path). The
     //    root (lane 63's R) takes node 0's chosen child when node 0 is on the path, else slot 127's value: lane 0
-    //    forms it and lane 63 takes it by one DPP wave rotate;
-    //  * push: vnew enters slot 127 and climbs the chain of its ancestors (slots 63, 31, 15, 7, 3, 1: the L halves
-    //    of lanes 31, 15, 7, 3, 1, 0; then the root). Chain holder c takes its father, slot c, whose post-pop value
-    //    is lane c's own chv (or slot 127's value) if lane c >> 1 is on the path and took its L child, else its
+    //    forms it and lane 63 takes it by one DPP wave rotate. Both of the pop's compares can have two popped
+    //    operands, so both go through N (the struct's comment);
+    //  * push: vnew (live) enters slot 127 and climbs the chain of its ancestors (slots 63, 31, 15, 7, 3, 1: the L
+    //    halves of lanes 31, 15, 7, 3, 1, 0; then the root). Chain holder c takes its father, slot c, whose post-pop
+    //    value is lane c's own chv (or slot 127's value) if lane c >> 1 is on the path and took its L child, else its
     //    pre-pop value; lane 0's father is the root.
     // Straight-line, and every decision is a per-lane test on the vector unit (the scalar unit only counts h and
     // combines two masks): the scalar-issue share of the hop is what bounds the kernel. The
     // caller reads the new root from lane 63's R.
-    __device__ __forceinline__ void replace128(uint64_t vnew, int32_t vnewI, const PathConst &pc, int lane)
+    __device__ __forceinline__ void replace128(uint64_t vnew, const PathConst &pc, int lane)
     {
         const uint64_t val = readlane64(L, 63); // slot 127
-        const int32_t valI = readlane32(IL, 63);
-        const uint64_t lm = ballot(L > R) | (1ull << 63); // node p takes its L child (node 63: slot 127 only)
+        const uint64_t valN = normk(val);       // on the scalar unit
+        const uint64_t lm = ballot(normk(L) > normk(R)) | (1ull << 63); // node p takes its L child (node 63: slot 127 only)
         const bool takeL = in_mask(lm);
         const uint64_t chv = takeL ? L : R;
-        const int32_t chI = takeL ? IL : IR;
         const uint32_t caddr = takeL ? pc.addrL : pc.addrR;
         const uint64_t up0 = bperm64_addr(chv, caddr);
-        const int32_t up0I = bperm32_addr(chI, caddr);
         const uint64_t fpre = bperm64_addr(L, pc.addrHalf);
-        const int32_t fpreI = bperm32_addr(IL, pc.addrHalf);
-        // keep the six fetches together: left to itself the compiler issues the father fetch after the first wait,
+        // keep the four fetches together: left to itself the compiler issues the father fetch after the first wait,
         // which makes two LDS round trips of the one (profiles/r04/ab_search_replace_fetch_pin.txt)
         __builtin_amdgcn_sched_barrier(0);
-        const uint64_t mv = ballot(!(val > chv));
+        const uint64_t mv = ballot(!(valN > normk(chv)));
         const uint64_t W = pc.path(mv, lm);
         // per-lane tests: the path is a chain of nodes, so its deepest node is W's highest bit
         // s_flbit of 0 is -1, so W = 0 gives 63 ^ -1 = -64: no lane and no half, no zero test needed
@@ -348,7 +333,6 @@ struct Heap {
         // of a VGPR copy. Lane 0: the root after the pop -- node 0's chosen child if node 0 is on the path, else val
         // (only lane 0 is read: with node 0 on the path val goes to lane 1)
         const uint64_t rootpp = writelane64(chv, val, (uint32_t)W & 1u);
-        const int32_t rootppI = writelane32(chI, valI, (uint32_t)W & 1u);
         // the chain's fathers after the pop, from the pre-pop registers (read on the chain lanes 0, 1, 3, 7, 15, 31,
         // 63 only): the moved child, or L before the pop; chain lane 2 lastW + 1 takes val when the path's end took
         // its L child (else the write goes to lane 2, off the chain); lane 0's father is the root
@@ -356,24 +340,17 @@ struct Heap {
         // tests a zero bit)
         const uint32_t kl = (((uint64_t)wlm >> (lastW & 63u)) & 1u) ? 2u * lastW + 1u : 2u;
         uint64_t fl = writelane64(moved ? chv : fpre, val, kl);
-        int32_t flI = writelane32(moved ? chI : fpreI, valI, kl);
         const bool s1 = in_mask(1ull);
         fl = s1 ? rootpp : fl;
-        flI = s1 ? rootppI : flI;
         // pop writes: the path nodes' chosen child slots (the path's end takes val; with no path the write to lane
         // 0 is never read), and the root
         const uint64_t up = writelane64(up0, val, lastW);
-        const int32_t upI = writelane32(up0I, valI, lastW);
         const bool wl = in_mask(W & lm), wr = in_mask(W & ~lm);
         L = wl ? up : L;
-        IL = wl ? upI : IL;
         R = wr ? up : R;
-        IR = wr ? upI : IR;
         const bool s63 = in_mask(1ull << 63);
         const uint64_t nroot = ((uint64_t)dpp_rol1_u32(hi32(rootpp)) << 32) | dpp_rol1_u32(lo32(rootpp)); // lane 63 <- lane 0
-        const int32_t nrootI = (int32_t)dpp_rol1_u32((uint32_t)rootppI);
         R = s63 ? nroot : R;
-        IR = s63 ? nrootI : IR;
         // push: h = the chain's ancestors below vnew after the pop: the L halves of lanes 31, 15, 7, 3, 1, 0 (slots 63 ..
         // 1) and lane 63's R (the root, index 7)
         constexpr uint64_t kChainL = (1ull << 31) | (1ull << 15) | (1ull << 7) | (1ull << 3) | (1ull << 1) | 1ull;
@@ -382,26 +359,21 @@ struct Heap {
         // index h takes vnew: chain lane (64 >> h) - 1's L (h = 7 writes lane 63's L, which the next select restores),
         // or lane 63's R (the root) when h = 7; the chain indices below h take their father's value
         L = writelane64(L, vnew, (64u >> h) - 1u);
-        IL = writelane32(IL, vnewI, (64u >> h) - 1u);
         const bool sh = pc.cidx < h;
         L = sh ? fl : L;
-        IL = sh ? flI : IL;
-        if (h == 7u) {
+        if (h == 7u)
             R = writelane64(R, vnew, 63u);
-            IR = writelane32(IR, vnewI, 63u);
-        }
     }
 
-    // faiss heap_push(k, val) while the ef = 128 heap fills (2 <= k <= 128): val enters slot k - 1 and sifts up its
-    // ancestors. Lane-mask form: each half finds its chain index (1-based position x is on the chain of k at index
+    // faiss heap_push(k, val) while the ef = 128 heap fills (2 <= k <= 128): val (live) enters slot k - 1 and sifts up
+    // its ancestors. Lane-mask form: each half finds its chain index (1-based position x is on the chain of k at index
     // m = bitlen(k) - bitlen(x) iff k >> m == x; lane 63's R, the root, is always on it, at index bitlen(k) - 1); the
     // ancestors below val are a bottom prefix of length h (heap order), the halves of index < h take their father's
     // value (one ds_bpermute round trip, issued first) and the half of index h takes val. No branch, no scalar
     // bookkeeping: the root is not tracked here (the caller reads it once the heap is full).
-    __device__ __forceinline__ void push_fill(uint32_t k, uint64_t val, int32_t valI, const PathConst &pc)
+    __device__ __forceinline__ void push_fill(uint32_t k, uint64_t val, const PathConst &pc)
     {
         const uint64_t fL = bperm64_addr(L, pc.addrF), fR = bperm64_addr(R, pc.addrF);
-        const int32_t fIL = bperm32_addr(IL, pc.addrF), fIR = bperm32_addr(IR, pc.addrF);
         const uint32_t B = (uint32_t)bitlen(k);
         const bool s63 = in_mask(1ull << 63);
         // m < 0 (x deeper than k) wraps to a shift of 57..63: the 64-bit shift gives 0, never a position
@@ -414,16 +386,11 @@ struct Heap {
         const uint32_t h = (uint32_t)(__builtin_popcountll(ballot(val > L) & aL) + __builtin_popcountll(ballot(val > R) & aR));
         const bool odd = in_mask(0xAAAAAAAAAAAAAAAAull); // father slot p odd: an L half
         const uint64_t f = odd ? fL : fR;
-        const int32_t fI = odd ? fIL : fIR;
         const bool wl = ciL < h, wr = ciR < h, xl = ciL == h, xr = ciR == h;
         L = wl ? f : L;
-        IL = wl ? fI : IL;
         L = xl ? val : L;
-        IL = xl ? valI : IL;
         R = wr ? f : R;
-        IR = wr ? fI : IR;
         R = xr ? val : R;
-        IR = xr ? valI : IR;
     }
 };
 
@@ -680,15 +647,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void hn
         Heap hp;
         hp.L = kUnused;
         hp.R = lane == 63 ? pack(dn, nearest) : kUnused;
-        // node ids are held tagged (id ^ 2^31, the low word of their key): the pushed key's low word is the id as read,
-        // no scalar XOR per push; an empty slot holds the tag of -1
-        hp.IL = (int32_t)0x7FFFFFFF;
-        hp.IR = lane == 63 ? (int32_t)((uint32_t)nearest ^ 0x80000000u) : (int32_t)0x7FFFFFFF;
+        // node ids are held tagged (id ^ 2^31, a live key's low word): the pushed key's low word is the id as read,
+        // no scalar XOR per push
         int kc = 1;
-        // the root's key (high word) and node id, current whenever the heap is full (kc == ef): the fill does not track
-        // them, they are read from lane 63's R once the heap is full, and after every full-heap replace
+        // the root's key (high word and low word w; its node, tagged, is w | 2^31), current whenever the heap is full
+        // (kc == ef): the fill does not track them, they are read from lane 63's R once the heap is full, and after
+        // every full-heap replace
         uint32_t rootHi = dn;
-        int32_t rootI = (int32_t)((uint32_t)nearest ^ 0x80000000u); // tagged
+        uint32_t rootW = (uint32_t)nearest ^ 0x80000000u;
         // result set: the log (LOGRES) or a sorted register set of k <= 64 entries
         int logn = 0;
         uint64_t rv = ~0ull; // !LOGRES: lane j < k holds the j-th smallest (key, id) so far
@@ -763,7 +729,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void hn
             // raised issue priority, so waves about to fetch their next row get ahead of waves in the push loop (whose
             // load is already in flight): 86.87 -> 86.45 ms at C5
             // pop_min: smallest key among valid slots, ties -> the highest slot
-            const bool vL = lo32(hp.L) != kPopLo, vR = lo32(hp.R) != kPopLo;
+            const bool vL = (int32_t)lo32(hp.L) < 0, vR = (int32_t)lo32(hp.R) < 0; // bit 31 of w
             // MinimaxHeap::size(): the valid (filled, not popped) slots; unused slots read as popped
             const uint64_t validm = ballot(vL) | ballot(vR);
             if (validm == 0ull)
@@ -790,10 +756,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void hn
             const int wl = tiedm ? 63 - __builtin_clzll(tiedm) : 63;
             const int32_t v0 = (int32_t)((uint32_t)__builtin_amdgcn_readlane((int)lo32(pickR ? hp.R : hp.L), wl) ^
                                          0x80000000u);
-            // mark the slot popped (its id -1 in the key; IL / IR keep the node)
+            // mark the slot popped: bit 31 of its w cleared, which leaves v0 itself (one select of the scalar per half;
+            // the key keeps the node)
             const bool popR = lane == wl && pickR, popL = lane == wl && !pickR;
-            hp.R = popR ? (hp.R & ~0xFFFFFFFFull) | kPopLo : hp.R;
-            hp.L = popL ? (hp.L & ~0xFFFFFFFFull) | kPopLo : hp.L;
+            hp.R = popR ? (hp.R & ~0xFFFFFFFFull) | (uint32_t)v0 : hp.R;
+            hp.L = popL ? (hp.L & ~0xFFFFFFFFull) | (uint32_t)v0 : hp.L;
             DRM_DBG(2u, q, nstep, (uint32_t)v0, d0, (uint32_t)__builtin_popcountll(validm), (uint32_t)kc, rootHi);
             // count_below(d0): every slot in the heap (popped ones included); unused keys are ~0. The slot just popped
             // holds d0 itself, so at most ef - 1 slots lie below it: with efSearch >= ef (ef = max(efSearch, k), so
@@ -924,12 +891,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void hn
                         add_result(val);
                     ++kc;
                     if (ef == 128)
-                        hp.push_fill((uint32_t)kc, val, idl, pconst);
+                        hp.push_fill((uint32_t)kc, val, pconst);
                     else
-                        hp.push(kc, val, idl, lane);
+                        hp.push(kc, val, lane);
                     if (kc == ef) { // full: the root is read once, and kept current from here on
                         rootHi = hp.root_hi();
-                        rootI = hp.root_id();
+                        rootW = hp.root_w();
                         break;
                     }
                 }
@@ -948,18 +915,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void hn
                 DRM_DBG(4u, q, nstep, (uint32_t)idl, key, (uint32_t)kc, 0u, (uint32_t)sn);
                 if (!LOGRES && key < thr)
                     add_result(val);
-                const uint32_t evk = rootHi; // the evicted slot: the root (its node id in rootI)
-                const int32_t evi = rootI;
+                const uint32_t evk = rootHi; // the evicted slot: the root (its node id, popped or not, in rootW)
+                const uint32_t evw = rootW;
                 if (ef == 128) {
-                    hp.replace128(val, idl, pconst, lane);
+                    hp.replace128(val, pconst, lane);
                     if (STAMPS)
                         st_acc[11] += 1u;
                 } else {
                     hp.pop(kc, lane);
-                    hp.push(kc, val, idl, lane);
+                    hp.push(kc, val, lane);
                 }
                 rootHi = hp.root_hi();
-                rootI = hp.root_id();
+                rootW = hp.root_w();
                 // the root fell: links at or above it leave the candidate mask (one compare for the rest of the row)
                 rem &= ballot(dall < rootHi);
                 // LOGRES: an evicted result at the new root's distance can still be among the k results (the result
@@ -969,7 +936,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void hn
                         log_flush();
                     const bool at = lane == sn; // lane sn takes the entry (one compare, two selects)
                     sbh = at ? evk : sbh;
-                    sbl = at ? (uint32_t)evi : sbl; // already tagged
+                    sbl = at ? (evw | kLive) : sbl; // the node, tagged
                     ++sn;
                 }
             }
@@ -990,14 +957,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void hn
             if (logn + kc > a.log_cap)
                 log_compact();
             {
-                const bool hl = hp.IL != (int32_t)0x7FFFFFFF, hr = hp.IR != (int32_t)0x7FFFFFFF; // filled slots
+                const bool hl = lo32(hp.L) != kPopLo, hr = lo32(hp.R) != kPopLo; // filled slots (kUnused's w is no id)
                 const uint64_t mL = ballot(hl), mR = ballot(hr), below = lanes_below(lane);
                 if (hl)
-                    __hip_atomic_store(lg + logn + __builtin_popcountll(mL & below), ((uint64_t)hi32(hp.L) << 32) | (uint32_t)hp.IL,
+                    __hip_atomic_store(lg + logn + __builtin_popcountll(mL & below), hp.L | kLive,
                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (hr)
                     __hip_atomic_store(lg + logn + __builtin_popcountll(mL) + __builtin_popcountll(mR & below),
-                                       ((uint64_t)hi32(hp.R) << 32) | (uint32_t)hp.IR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                       hp.R | kLive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #ifdef DRM_PQ_DEBUG
                 if (__builtin_popcountll(mL) + __builtin_popcountll(mR) != kc && lane == 0)
                     printf("[pq dbg] q %d: %d heap slots hold an id, %d filled\n", q,

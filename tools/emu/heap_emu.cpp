@@ -1,6 +1,6 @@
 // Host emulation of the lean search kernel's wave-parallel MinimaxHeap (tools/emu/wave_emu.h: Heap::replace128,
-// Heap::push_fill, pop_min's slot marking, Heap::holds) against a literal faiss MinimaxHeap that also keeps the node
-// id of every slot: random push / pop_min sequences with many equal distances; any divergence of keys, ids, the root
+// Heap::push_fill, pop_min's slot marking -- bit 31 of the key's low word cleared, the node id kept --, Heap::holds)
+// against a literal faiss MinimaxHeap that also keeps the node id of every slot: random push / pop_min sequences with many equal distances; any divergence of keys, ids, the root
 // or heap membership is reported with the step. Test infrastructure: g++ -O2 -std=c++17 heap_emu.cpp -o heap_emu
 #include "wave_emu.h"
 
@@ -47,7 +47,7 @@ struct Ref {
 };
 
 static u64 slot_key(const Heap &h, int s) { if (s == 0) return h.R[63]; int o = (s - 1) >> 1; return (s & 1) ? h.L[o] : h.R[o]; }
-static int32_t slot_id(const Heap &h, int s) { if (s == 0) return h.IR[63]; int o = (s - 1) >> 1; return (s & 1) ? h.IL[o] : h.IR[o]; }
+static int32_t slot_id(const Heap &h, int s) { return node_of(slot_key(h, s)); }
 static u64 &slot_key_ref(Heap &h, int s) { if (s == 0) return h.R[63]; int o = (s - 1) >> 1; return (s & 1) ? h.L[o] : h.R[o]; }
 
 int main(int argc, char **argv)
@@ -60,42 +60,44 @@ int main(int argc, char **argv)
         // every other trial: a smaller heap (ef < 128), the kernel's general Heap::pop / Heap::push path
         const int n = (t & 1) ? 2 + (int)(rng() % 126) : 128;
         Heap hp; Ref ref(n);
-        for (int l = 0; l < W; ++l) { hp.L[l] = kUnused; hp.R[l] = kUnused; hp.IL[l] = -1; hp.IR[l] = -1; }
+        hp.init();
         const int nd = 2 + (int)(rng() % 40); // few distinct distances: ties
         int32_t next_id = 0;
-        u64 root = 0; int32_t rootI = -1; int kc = 0;
+        u64 root = 0; int kc = 0;
         auto push = [&](u32 key, int32_t id) {
             // the kernel: full heap -> reject at or above the root, else replace; filling -> push_fill
             const bool ok_ref = ref.push(id, key);
             if (kc == 0) { // first push: the entry (hp.R[63] = root)
-                hp.R[63] = pack(key, id); hp.IR[63] = id; root = hp.R[63]; rootI = id; kc = 1;
+                hp.R[63] = pack(key, id); root = hp.R[63]; kc = 1;
             } else if (kc == n) {
                 if (key >= hi32(root)) { if (ok_ref) { std::printf("trial %d: reject mismatch\n", t); std::exit(1); } return; }
                 if (n == 128) {
-                    root = hp.replace128(pack(key, id), id, pc, rootI);
+                    root = hp.replace128(pack(key, id), pc);
                 } else {
-                    hp.pop(kc); hp.push(kc, pack(key, id), id); root = hp.R[63]; rootI = hp.IR[63];
+                    hp.pop(kc); hp.push(kc, pack(key, id)); root = hp.R[63];
                 }
             } else if (n == 128) {
-                ++kc; hp.push_fill(kc, pack(key, id), id, pc); root = hp.R[63]; rootI = hp.IR[63];
+                ++kc; hp.push_fill(kc, pack(key, id), pc); root = hp.R[63];
             } else {
-                ++kc; hp.push(kc, pack(key, id), id); root = hp.R[63]; rootI = hp.IR[63];
+                ++kc; hp.push(kc, pack(key, id)); root = hp.R[63];
             }
             if (!ok_ref) { std::printf("trial %d: accept mismatch\n", t); std::exit(1); }
         };
         for (int step = 0; step < 2000; ++step) {
             if (rng() % 3 || kc == 0) {
                 push((u32)(rng() % nd) + 0x80000000u, next_id++);
-            } else { // pop_min as the kernel marks it: the slot's key low word -> kPopLo
+            } else { // pop_min as the kernel marks it: bit 31 of the slot's key low word cleared
                 const int s = ref.pop_min();
                 if (s < 0) continue;
                 u64 &kk = slot_key_ref(hp, s);
-                kk = (kk & ~0xFFFFFFFFull) | kPopLo;
-                if (s == 0) root = (root & ~0xFFFFFFFFull) | kPopLo;
+                kk = mark_popped(kk);
+                if (s == 0) root = mark_popped(root);
             }
             for (int s = 0; s < ref.k; ++s) {
+                // faiss's key (popped: id -1) is the slot's key through N; the raw key holds the node, live or popped
                 const u64 want = ((u64)ref.dis[s] << 32) | (u32)((u32)ref.ids[s] ^ 0x80000000u);
-                if (slot_key(hp, s) != want || slot_id(hp, s) != ref.node[s]) {
+                const u64 raw = ((u64)ref.dis[s] << 32) | ((u32)ref.node[s] | (ref.ids[s] == -1 ? 0u : kLive));
+                if (normk(slot_key(hp, s)) != want || slot_key(hp, s) != raw || slot_id(hp, s) != ref.node[s]) {
                     std::printf("trial %d step %d slot %d: key %016llx want %016llx id %d want %d\n", t, step, s,
                                 (unsigned long long)slot_key(hp, s), (unsigned long long)want, slot_id(hp, s), ref.node[s]);
                     std::exit(1);

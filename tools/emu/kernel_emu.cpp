@@ -18,11 +18,11 @@ extern "C" int emu_search_one(const int32_t *nbr0, const uint8_t *codes, int64_t
     const int ef = 128, k = 128, ef_search = 128, log_cap = 512;
     auto adc = [&](int32_t v) { float r = 0.0f; for (int m = 0; m < 8; ++m) r = r + lut[m * 256 + codes[(size_t)v * 8 + m]]; return ord32(r); };
     Heap hp;
-    for (int l = 0; l < W; ++l) { hp.L[l] = kUnused; hp.R[l] = kUnused; hp.IL[l] = -1; hp.IR[l] = -1; }
+    hp.init();
     const u32 dn = ord32(dnear);
-    hp.R[63] = pack(dn, nearest); hp.IR[63] = nearest;
+    hp.R[63] = pack(dn, nearest);
     int kc = 1, nvalid = 1;
-    u64 root = pack(dn, nearest); int32_t rootI = nearest;
+    u64 root = pack(dn, nearest); // the root's key: its node, popped or not, is node_of(root)
     std::vector<u64> lg;        // tied evictions (the kernel's log before the heap's entries join it)
     std::vector<int32_t> pushed{nearest}; // every accepted push, for the duplicate check
     int nstep = 0, maxlog = 0;
@@ -34,7 +34,7 @@ extern "C" int emu_search_one(const int32_t *nbr0, const uint8_t *codes, int64_t
         bool vL[W], vR[W]; u32 cL[W], cR[W], pk[W]; bool pickR[W];
         u32 d0 = 0xFFFFFFFFu;
         for (int l = 0; l < W; ++l) {
-            vL[l] = lo32(hp.L[l]) != kPopLo; vR[l] = lo32(hp.R[l]) != kPopLo;
+            vL[l] = is_live(hp.L[l]); vR[l] = is_live(hp.R[l]);
             cL[l] = vL[l] ? hi32(hp.L[l]) : 0xFFFFFFFFu; cR[l] = vR[l] ? hi32(hp.R[l]) : 0xFFFFFFFFu;
             pickR[l] = cR[l] < cL[l] || (cR[l] == cL[l] && l != 63);
             pk[l] = pickR[l] ? cR[l] : cL[l]; d0 = std::min(d0, pk[l]);
@@ -46,8 +46,8 @@ extern "C" int emu_search_one(const int32_t *nbr0, const uint8_t *codes, int64_t
         if (tiedm) { wl = 63 - __builtin_clzll(tiedm); wR = (rightm >> wl) & 1ull; }
         const int32_t v0 = (int32_t)(lo32(wR ? hp.R[wl] : hp.L[wl]) ^ 0x80000000u);
         if (v0 < 0 || v0 >= ntotal) { std::printf("bad v0 %d at hop %d (d0 %08x nvalid %d)\n", v0, nstep, d0, nvalid); return -2; }
-        if (wR) hp.R[wl] = (hp.R[wl] & ~0xFFFFFFFFull) | kPopLo; else hp.L[wl] = (hp.L[wl] & ~0xFFFFFFFFull) | kPopLo;
-        if (wl == 63 && wR) root = (root & ~0xFFFFFFFFull) | kPopLo;
+        if (wR) hp.R[wl] = mark_popped(hp.R[wl]); else hp.L[wl] = mark_popped(hp.L[wl]); // bit 31 cleared, the node kept
+        if (wl == 63 && wR) root = mark_popped(root);
         nvalid--;
         int below = 0; for (int l = 0; l < W; ++l) below += (hi32(hp.L[l]) < d0) + (hi32(hp.R[l]) < d0);
         if (below >= ef_search) break;
@@ -63,8 +63,8 @@ extern "C" int emu_search_one(const int32_t *nbr0, const uint8_t *codes, int64_t
                 const u32 hv = pop_hash(v1[l]);
                 const bool kp = (popped_bits[(hv >> 5) & 63u] >> (hv & 31u)) & 1u;
                 const u32 dp = (l < jmax && !kp) ? dall[l] : 0xFFFFFFFFu;
-                const u32 hL = lo32(hp.L[l]) != kPopLo ? hi32(hp.L[l]) : 0xFFFFFFFFu;
-                const u32 hR = lo32(hp.R[l]) != kPopLo ? hi32(hp.R[l]) : 0xFFFFFFFFu;
+                const u32 hL = is_live(hp.L[l]) ? hi32(hp.L[l]) : 0xFFFFFFFFu;
+                const u32 hR = is_live(hp.R[l]) ? hi32(hp.R[l]) : 0xFFFFFFFFu;
                 u32 mk = std::min(dp, std::min(hL, hR));
                 const int32_t mid = dp == mk ? v1[l] : (hL == mk ? (int32_t)(lo32(hp.L[l]) ^ 0x80000000u) : (int32_t)(lo32(hp.R[l]) ^ 0x80000000u));
                 if (mk < mm) { mm = mk; pr = mid; }
@@ -80,11 +80,11 @@ extern "C" int emu_search_one(const int32_t *nbr0, const uint8_t *codes, int64_t
                 const u32 key = dall[l]; const int32_t idl = v1[l];
                 if (hp.holds(idl)) continue;
                 ++kc;
-                hp.push_fill(kc, pack(key, idl), idl, pc);
+                hp.push_fill(kc, pack(key, idl), pc);
                 ++nvalid;
                 pushed.push_back(idl);
                 if (kc == ef) { // the root is read once the heap is full (push_fill does not track it)
-                    root = hp.R[63]; rootI = hp.IR[63];
+                    root = hp.R[63];
                     break;
                 }
             }
@@ -96,22 +96,22 @@ extern "C" int emu_search_one(const int32_t *nbr0, const uint8_t *codes, int64_t
             if (key >= hi32(root)) { std::printf("candidate at or above the root at hop %d\n", nstep); return -5; }
             const int32_t idl = v1[l];
             if (hp.holds(idl)) continue;
-            const u32 evk = hi32(root); const int32_t evi = rootI;
-            nvalid += lo32(root) == kPopLo ? 1 : 0;
-            root = hp.replace128(pack(key, idl), idl, pc, rootI);
+            const u32 evk = hi32(root); const int32_t evi = node_of(root);
+            nvalid += is_live(root) ? 0 : 1;
+            root = hp.replace128(pack(key, idl), pc);
             rem &= below_root(); // the root fell: links at or above it leave the mask
             if (evk == hi32(root)) lg.push_back(pack(evk, evi));
             pushed.push_back(idl);
         }
-        if (kc == ef && (hp.R[63] != root || hp.IR[63] != rootI)) { std::printf("root not current at hop %d\n", nstep); return -4; }
+        if (kc == ef && hp.R[63] != root) { std::printf("root not current at hop %d\n", nstep); return -4; }
         maxlog = std::max<int>(maxlog, (int)lg.size());
         nstep++;
     }
     // the k results: the heap's entries (node ids) plus the log, every entry below T = the root's key, then the
     // smallest ids at T (log_id_threshold / log_select)
     for (int l = 0; l < W; ++l) {
-        if (hp.IL[l] >= 0) lg.push_back(pack(hi32(hp.L[l]), hp.IL[l]));
-        if (hp.IR[l] >= 0) lg.push_back(pack(hi32(hp.R[l]), hp.IR[l]));
+        if (lo32(hp.L[l]) != kPopLo) lg.push_back(pack(hi32(hp.L[l]), node_of(hp.L[l]))); // filled slots
+        if (lo32(hp.R[l]) != kPopLo) lg.push_back(pack(hi32(hp.R[l]), node_of(hp.R[l])));
     }
     const u32 T = kc == ef ? hi32(root) : 0xFFFFFFFFu;
     std::vector<u64> sel, eq;
