@@ -11,7 +11,8 @@
 //     after N(w) = max(w, 2^31 - 1) where both sides can be popped (struct Heap has the argument);
 //   * the heap sits in the sibling-pair layout (lane p holds the children of node p, slots 2p+1 and
 //     2p+2; the root is lane 63's second half); a full-heap replace finds its sift-down path from two
-//     ballots and per-lane ancestor masks, and its sift-up chain by one parallel compare;
+//     ballots and per-lane ancestor masks, and the pushed value then climbs on the scalar unit, level by level with
+//     an early exit (lane reads and writes of the one father chain, no cross-lane fetch);
 //   * pop_min checks the previous hop's prediction of the minimum with two ballots (a 32-bit DPP min
 //     only when it missed) and takes the highest tied slot from lane masks;
 //   * result set at k == ef: the HeapBlockResultHandler (k = ef) holds, at every step, the same
@@ -73,6 +74,17 @@ __device__ __forceinline__ uint64_t readlane64(uint64_t v, int l)
     const uint32_t h = (uint32_t)__builtin_amdgcn_readlane((int)hi32(v), l);
     const uint32_t o = (uint32_t)__builtin_amdgcn_readlane((int)lo32(v), l);
     return ((uint64_t)h << 32) | o;
+}
+// a > b for two wave-uniform keys, on the scalar unit: b - a borrows. The ISA has no ordered 64-bit scalar compare,
+// and the compiler's own form copies one key into a VGPR pair for a v_cmp_gt_u64 (two vector instructions).
+__device__ __forceinline__ bool sgt64(uint64_t a, uint64_t b)
+{
+    uint32_t r;
+    asm("s_sub_u32 %0, %1, %3\n\ts_subb_u32 %0, %2, %4\n\ts_cselect_b32 %0, 1, 0"
+        : "=&s"(r)
+        : "s"(lo32(b)), "s"(hi32(b)), "s"(lo32(a)), "s"(hi32(a))
+        : "scc");
+    return r != 0u;
 }
 __device__ __forceinline__ uint32_t bperm32(uint32_t v, int src)
 {
@@ -152,20 +164,16 @@ struct PathConst {
     // itself: the low halves are kept, and Ahi is p's own bit for p >= 32 (0 below)
     uint32_t Alo, Ahi, Auplo, Lreqlo;
     // ds_bpermute byte addresses: this lane's left / right child lane (slots 2p+1, 2p+2 are held by lanes 2p+1, 2p+2
-    // mod 64), and its parent in the chain of slot 127's ancestors (lane >> 1)
-    uint32_t addrL, addrR, addrHalf, half; // half = lane >> 1
+    // mod 64)
+    uint32_t addrL, addrR;
     // heap filling (push_fill): this lane's halves are the 1-based positions xL = 2p+2 and 2p+3 (lane 63's R: the root,
     // position 1), both of bit length bl; their father is slot p, held by lane (p-1)/2 (its L half when p is odd, its
     // R half when p is even) and, for p = 0, by lane 63's R (the root)
     uint32_t xL, bl, addrF;
-    // full-heap push: the chain index of this lane's L half on slot 127's ancestor chain (slot 127 = 0, 63 = 1, 31 = 2,
-    // 15 = 3, 7 = 4, 3 = 5, 1 = 6: lanes 63, 31, 15, 7, 3, 1, 0; the root, lane 63's R, is 7); 15 for every other lane
-    uint32_t cidx;
     __device__ explicit PathConst(int lane)
         : addrL((uint32_t)((2 * lane + 1) & 63) << 2), addrR((uint32_t)((2 * lane + 2) & 63) << 2),
-          addrHalf((uint32_t)(lane >> 1) << 2), half((uint32_t)lane >> 1), xL(2u * (uint32_t)lane + 2u),
-          bl((uint32_t)bitlen(2u * (uint32_t)lane + 2u)), addrF(lane > 0 ? (uint32_t)((lane - 1) >> 1) << 2 : 63u << 2),
-          cidx(((lane + 1) & lane) == 0 ? 6u - (uint32_t)(31 - __builtin_clz((uint32_t)lane + 1u)) : 15u)
+          xL(2u * (uint32_t)lane + 2u), bl((uint32_t)bitlen(2u * (uint32_t)lane + 2u)),
+          addrF(lane > 0 ? (uint32_t)((lane - 1) >> 1) << 2 : 63u << 2)
     {
         uint64_t A = 1ull << lane, Aup = 0, Lreq = 0;
         for (int c = lane; c > 0;) {
@@ -291,8 +299,8 @@ struct Heap {
             R = val;
     }
 
-    // heap_pop(128) then heap_push(128, vnew) on the full ef = 128 heap (MinimaxHeap::push when k == n), with the
-    // cross-lane fetches issued together from the pre-pop registers: one ds_bpermute round trip per replace.
+    // heap_pop(128) then heap_push(128, vnew) on the full ef = 128 heap (MinimaxHeap::push when k == n): the pop on
+    // the vector unit with one ds_bpermute round trip, then the push as a scalar climb on the post-pop registers.
     //  * pop: slot 127 (lane 63's L) is sifted down from the root. Lane p on the path writes its chosen child slot
     //    with that child's own chosen child (chv of lane ch_p), or with slot 127's value when p is the path's last
     //    node; the path is the set of lanes whose own and ancestors' chosen children move up (PathConst::path). The
@@ -300,12 +308,12 @@ struct Heap {
     //    forms it and lane 63 takes it by one DPP wave rotate. Both of the pop's compares can have two popped
     //    operands, so both go through N (the struct's comment);
     //  * push: vnew (live) enters slot 127 and climbs the chain of its ancestors (slots 63, 31, 15, 7, 3, 1: the L
-    //    halves of lanes 31, 15, 7, 3, 1, 0; then the root). Chain holder c takes its father, slot c, whose post-pop
-    //    value is lane c's own chv (or slot 127's value) if lane c >> 1 is on the path and took its L child, else its
-    //    pre-pop value; lane 0's father is the root.
-    // Straight-line, and every decision is a per-lane test on the vector unit (the scalar unit only counts h and
-    // combines two masks): the scalar-issue share of the hop is what bounds the kernel. The
-    // caller reads the new root from lane 63's R.
+    //    halves of lanes 31, 15, 7, 3, 1, 0; then the root) after the pop's writes, level by level with an early exit
+    //    (climb128). Until round 10 the climb ran beside the pop, straight-line on the vector unit: every chain
+    //    holder fetched its father's post-pop value from the pre-pop registers (a second ds_bpermute pair, a moved
+    //    test, two writelanes and three selects), whether vnew moved or not.
+    // The pop is straight-line and every decision in it a per-lane test; the kernel is bound by vector issue, and the
+    // scalar unit has room ("Round 10"). The caller reads the new root from lane 63's R.
     __device__ __forceinline__ void replace128(uint64_t vnew, const PathConst &pc, int lane)
     {
         const uint64_t val = readlane64(L, 63); // slot 127
@@ -315,9 +323,7 @@ struct Heap {
         const uint64_t chv = takeL ? L : R;
         const uint32_t caddr = takeL ? pc.addrL : pc.addrR;
         const uint64_t up0 = bperm64_addr(chv, caddr);
-        const uint64_t fpre = bperm64_addr(L, pc.addrHalf);
-        // keep the four fetches together: left to itself the compiler issues the father fetch after the first wait,
-        // which makes two LDS round trips of the one (profiles/r04/ab_search_replace_fetch_pin.txt)
+        // the fetch is issued before the path is worked out, not after it
         __builtin_amdgcn_sched_barrier(0);
         const uint64_t mv = ballot(!(valN > normk(chv)));
         const uint64_t W = pc.path(mv, lm);
@@ -326,22 +332,10 @@ struct Heap {
         uint32_t fb;
         asm("s_flbit_i32_b64 %0, %1" : "=s"(fb) : "s"(W));
         const uint32_t lastW = fb ^ 63u;
-        // lane (lane >> 1) is on the path and took its L child (lane >> 1 < 32: the low word holds its bit)
-        const uint32_t wlm = (uint32_t)(W & lm);
-        const bool moved = (wlm >> pc.half) & 1u;
         // the single-lane writes of slot 127's value (val) are v_writelanes of the scalar, not a compare and a select
         // of a VGPR copy. Lane 0: the root after the pop -- node 0's chosen child if node 0 is on the path, else val
         // (only lane 0 is read: with node 0 on the path val goes to lane 1)
         const uint64_t rootpp = writelane64(chv, val, (uint32_t)W & 1u);
-        // the chain's fathers after the pop, from the pre-pop registers (read on the chain lanes 0, 1, 3, 7, 15, 31,
-        // 63 only): the moved child, or L before the pop; chain lane 2 lastW + 1 takes val when the path's end took
-        // its L child (else the write goes to lane 2, off the chain); lane 0's father is the root
-        // (one 64-bit bit test: the low word of W & lm, zero-extended, so a path end at lane >= 32 -- or no path --
-        // tests a zero bit)
-        const uint32_t kl = (((uint64_t)wlm >> (lastW & 63u)) & 1u) ? 2u * lastW + 1u : 2u;
-        uint64_t fl = writelane64(moved ? chv : fpre, val, kl);
-        const bool s1 = in_mask(1ull);
-        fl = s1 ? rootpp : fl;
         // pop writes: the path nodes' chosen child slots (the path's end takes val; with no path the write to lane
         // 0 is never read), and the root
         const uint64_t up = writelane64(up0, val, lastW);
@@ -351,18 +345,39 @@ struct Heap {
         const bool s63 = in_mask(1ull << 63);
         const uint64_t nroot = ((uint64_t)dpp_rol1_u32(hi32(rootpp)) << 32) | dpp_rol1_u32(lo32(rootpp)); // lane 63 <- lane 0
         R = s63 ? nroot : R;
-        // push: h = the chain's ancestors below vnew after the pop: the L halves of lanes 31, 15, 7, 3, 1, 0 (slots 63 ..
-        // 1) and lane 63's R (the root, index 7)
-        constexpr uint64_t kChainL = (1ull << 31) | (1ull << 15) | (1ull << 7) | (1ull << 3) | (1ull << 1) | 1ull;
-        const uint32_t h = (uint32_t)__builtin_popcount((uint32_t)ballot(vnew > L) & (uint32_t)kChainL) +
-                           (uint32_t)(ballot(vnew > R) >> 63); // 32-bit scalar ops: the chain's L bits are in the low word
-        // index h takes vnew: chain lane (64 >> h) - 1's L (h = 7 writes lane 63's L, which the next select restores),
-        // or lane 63's R (the root) when h = 7; the chain indices below h take their father's value
-        L = writelane64(L, vnew, (64u >> h) - 1u);
-        const bool sh = pc.cidx < h;
-        L = sh ? fl : L;
-        if (h == 7u)
-            R = writelane64(R, vnew, 63u);
+        // push: slot 127 (lane 63's L) is free now, and vnew climbs from it on the registers the pop left
+        climb128(vnew);
+    }
+
+    // faiss heap_push(128, vnew) on the full heap's registers: vnew (live) climbs slot 127's ancestor chain -- the L
+    // halves of lanes 63 (slot 127 itself), 31, 15, 7, 3, 1, 0, each the father of the one before it (lane o's father
+    // on the chain is lane o >> 1), then the root (lane 63's R) -- on the scalar unit, faiss's loop literally.
+    // Everything in a sift-up is wave-uniform (the value, the father's slot, the compare); the heap merely lives in
+    // VGPR lanes. A level is two v_readlane, the scalar compare and two v_writelane, and the climb ends at the first
+    // father not below vnew; in the literal search of random graphs two pushes in three do not move at all
+    // (tests/test_gpu_heap_siftup.py counts them; DESIGN.md sec. 4.1, "Round 10").
+    // Written as a loop over the lane with a single exit and one final write (w into lane o's L), so that L is updated
+    // in place: the unrolled form, and a loop with an exit per compare, made the compiler copy L at every level.
+    __device__ __forceinline__ void climb128(uint64_t vnew)
+    {
+        uint32_t o = 63u; // the lane whose L is free
+        uint64_t f = readlane64(L, 31);
+        bool up = sgt64(vnew, f); // cmp2(vnew, father)
+#pragma nounroll
+        while (up) { // one exit: the compiler keeps L in place
+            L = writelane64(L, f, o);
+            o >>= 1;
+            f = readlane64(L, (int)(o >> 1)); // at o = 0 a value that decides nothing
+            up = (o != 0u) & sgt64(vnew, f);
+        }
+        uint64_t w = vnew;
+        if (o == 0u) { // lane 0's L is slot 1: its father is the root
+            const uint64_t r = readlane64(R, 63);
+            const bool top = sgt64(vnew, r);
+            R = writelane64(R, top ? vnew : r, 63u);
+            w = top ? r : vnew;
+        }
+        L = writelane64(L, w, o);
     }
 
     // faiss heap_push(k, val) while the ef = 128 heap fills (2 <= k <= 128): val (live) enters slot k - 1 and sifts up
@@ -371,6 +386,11 @@ struct Heap {
     // ancestors below val are a bottom prefix of length h (heap order), the halves of index < h take their father's
     // value (one ds_bpermute round trip, issued first) and the half of index h takes val. No branch, no scalar
     // bookkeeping: the root is not tracked here (the caller reads it once the heap is full).
+    // Round 10 measured the scalar form of this push (faiss's loop literally: the father by two v_readlane, a scalar
+    // compare, two v_writelane per level, early exit) and a hybrid (h as below, the h moves by lane reads and
+    // writes): both 2.0 ms slower at C5, so the lane-mask form stays ("Round 10"). The half of a
+    // lane a position lies in (L / R) depends on k, which costs the scalar form a branch per read and per write and
+    // the compiler's copies of R around them; climb128 has no such choice to make.
     __device__ __forceinline__ void push_fill(uint32_t k, uint64_t val, const PathConst &pc)
     {
         const uint64_t fL = bperm64_addr(L, pc.addrF), fR = bperm64_addr(R, pc.addrF);
