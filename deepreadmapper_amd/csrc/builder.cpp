@@ -478,16 +478,9 @@ extern "C" int drm_build_hnswpq(const float *x, int64_t n, int32_t d, int32_t M_
                                 int32_t efConstruction, double sample_rate, int32_t nthreads, uint64_t seed,
                                 const char *index_path)
 {
-    try {
+    return drm::guarded([&] {
         if (!x || !index_path)
             throw drm::Error(DRM_ERR_ARG, "null argument");
         drm::build_hnswpq(x, n, d, M_pq, nbits, M_hnsw, efConstruction, sample_rate, nthreads, seed, index_path);
-        return DRM_OK;
-    } catch (const drm::Error &e) {
-        drm::set_last_error(e.what());
-        return e.code;
-    } catch (const std::exception &e) {
-        drm::set_last_error(e.what());
-        return DRM_ERR_ARG;
-    }
+    });
 }

@@ -287,16 +287,9 @@ void build_hnsw_flat(const float *x, int64_t n, int d, int M, int efc, int nthre
 extern "C" int drm_build_hnsw_flat(const float *x, int64_t n, int32_t d, int32_t M, int32_t efc, int32_t nthreads,
                                    uint64_t seed, const char *path)
 {
-    try {
+    return drm::guarded([&] {
         if (!x || !path)
             throw drm::Error(DRM_ERR_ARG, "null argument");
         drm::build_hnsw_flat(x, n, d, M, efc, nthreads, seed, path);
-        return DRM_OK;
-    } catch (const drm::Error &e) {
-        drm::set_last_error(e.what());
-        return e.code;
-    } catch (const std::exception &e) {
-        drm::set_last_error(e.what());
-        return DRM_ERR_IO;
-    }
+    }, DRM_ERR_IO);
 }

@@ -650,16 +650,9 @@ extern "C" int drm_build_hnswpq_device(const float *d_x, int64_t n, int32_t d, i
                                        int32_t M_hnsw, int32_t efConstruction, double sample_rate, uint64_t seed,
                                        int device, const char *index_path)
 {
-    try {
+    return drm::guarded([&] {
         if (!d_x || !index_path)
             throw drm::Error(DRM_ERR_ARG, "null argument");
         drm::build_hnswpq_gpu(d_x, n, d, M_pq, nbits, M_hnsw, efConstruction, sample_rate, seed, device, index_path);
-        return DRM_OK;
-    } catch (const drm::Error &e) {
-        drm::set_last_error(e.what());
-        return e.code;
-    } catch (const std::exception &e) {
-        drm::set_last_error(e.what());
-        return DRM_ERR_ARG;
-    }
+    });
 }

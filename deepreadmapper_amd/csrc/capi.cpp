@@ -33,22 +33,7 @@ struct drm_encoder {
 
 using drm::Error;
 
-template <class F> static int guarded(F &&f)
-{
-    try {
-        f();
-        return DRM_OK;
-    } catch (const Error &e) {
-        drm::set_last_error(e.what());
-        return e.code;
-    } catch (const std::bad_alloc &) {
-        drm::set_last_error("out of host memory");
-        return DRM_ERR_ARG;
-    } catch (const std::exception &e) {
-        drm::set_last_error(e.what());
-        return DRM_ERR_ARG;
-    }
-}
+using drm::guarded;
 
 namespace {
 template <class T> struct DevBuf { // RAII device buffer for host-pointer entry points

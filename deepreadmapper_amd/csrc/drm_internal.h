@@ -1,6 +1,7 @@
 // deepreadmapper_amd/csrc/drm_internal.h -- private C++ API shared by the library and the CLIs.
 #pragma once
 #include <cstdint>
+#include <new>
 #include <stdexcept>
 #include <string>
 #include <unordered_map>
@@ -17,6 +18,25 @@ struct Error : std::runtime_error {
 };
 
 void set_last_error(const std::string &msg);
+
+// The body of an extern "C" entry point: runs f and turns what it throws into the call's return code and
+// drm_last_error's message. An Error gives its own code; anything else gives `other`.
+template <class F> int guarded(F &&f, int other = DRM_ERR_ARG)
+{
+    try {
+        f();
+        return DRM_OK;
+    } catch (const Error &e) {
+        set_last_error(e.what());
+        return e.code;
+    } catch (const std::bad_alloc &) {
+        set_last_error("out of host memory");
+        return other;
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        return other;
+    }
+}
 
 // RCCL helpers over a drm_comm (exec.cpp), for collectives the C ABI builds on (drm_index_broadcast, capi.cpp):
 // a grouped ncclBroadcast of byte ranges from `root` (send is read on the root only; recv may equal send there),
@@ -151,55 +171,64 @@ struct FastaContig {
     int64_t start = 0, len = 0;
 };
 std::vector<FastaContig> fasta_contigs(const std::string &path);
-// write_sam / write_sam_streaming (utils.cpp:336-503) for one block of queries: the SAM lines of
-// queries [q0, q0 + nq) whose ids[i][0 .. counts[i]) are dense window ids (ids[i] at ids + i * k).
-// `header` writes @HD / @SQ first (SN ref_name, LN ref_len: the reference's quirk) and truncates.
-// `aln` (the DRM_SAM_CIGAR mode, no reference counterpart: the reference's CIGAR is a TODO) gives the block's
-// rows their GPU alignment (drm_sw_align of window ids[i * k + j] with the tagged query q0 + i): row i * k + j has
-// record rec[i * k + j] and its complete operations at ops + ops_off[i * k + j]. The line is then
-//   QNAME FLAG ref POS 60 CIGAR * 0 0 SEQ * AS:i:<score> NM:i:<nm>
-// with the real leftmost POS, soft clips, and SEQ reverse-complemented under flag 16; a status-1 record is
-// written unmapped (FLAG | 4, POS 0, CIGAR *, no tags). Null: the reference's pseudo fields.
-// With region_start / region_len set (DRM_SAM_SCORING / DRM_SAM_FLANK: drm_sw_align_affine over the row's flanked
-// region, drm_sw_align_region) the record is relative to genome[region_start[row] ..+ region_len[row]) and the row is
-// formatted by drm_sam_cigar_region's rules; AS is then the affine score.
-// With md set (DRM_SAM_MD: drm_sw_align_md of the same rows) every mapped line ends in MD:Z:<drm_sam_md of the row>,
-// behind NM:i; row r has the record md[r] and its complete words at md_words + md_off[r].
+// ---------------------------------------------------------------------------------------------
+// SAM (sam.cpp): write_sam / write_sam_streaming (utils.cpp:336-503), one block of queries per call
+// ---------------------------------------------------------------------------------------------
+// The GPU alignment of every row of a block (the DRM_SAM_CIGAR mode, no reference counterpart: the reference's CIGAR
+// is a TODO). A row with a record is written with its real leftmost POS, soft clips, SEQ reverse-complemented and QUAL
+// reversed under flag 16, and the tags AS:i:<score> NM:i:<nm>; a status-1 record is written unmapped (FLAG | 4, POS 0,
+// CIGAR *, MAPQ 0, no tags).
 struct SamAlignments {
-    const drm_sw_alignment *rec;
-    const uint32_t *ops;
+    const drm_sw_alignment *rec; // drm_sw_align of the row's window with its tagged query
+    const uint32_t *ops;         // row r's complete operations start at ops + ops_off[r]
     const int64_t *ops_off;
+    // DRM_SAM_SCORING / DRM_SAM_FLANK (drm_sw_align_affine over the row's flanked region, drm_sw_align_region): the
+    // record is relative to genome[region_start[r] ..+ region_len[r]) and the row is formatted by drm_sam_cigar_region's
+    // rules; AS is then the affine score. Null: the window of the row's id (drm_sam_cigar).
     const int64_t *region_start = nullptr;
     const int32_t *region_len = nullptr;
+    // DRM_SAM_MD (drm_sw_align_md of the same rows): every mapped line gets MD:Z:<drm_sam_md of the row> behind NM:i;
+    // row r has the record md[r] and its complete words at md_words + md_off[r]
     const drm_sw_md *md = nullptr;
     const uint32_t *md_words = nullptr;
     const int64_t *md_off = nullptr;
 };
-// `ctg` (DRM_CONTIGS, with `aln` only; null = the one sequence ref_name): the contig table of the reference and the
-// contig of every row, indexed like ids. The header then holds one @SQ line per contig in file order (SN its name, LN
-// its length), a row's RNAME is its contig's name and its POS counts from the contig's start; write_sam_block writes a
-// query without rows as one unmapped line (flag 4). In write_sam_pairs an unmapped mate takes its mate's RNAME and POS;
-// mates on one contig print RNEXT "=", mates on two the other's name and local PNEXT, TLEN 0 and never flag 0x2.
+// DRM_CONTIGS: the contig table of the reference and the contig of every row. The header then holds one @SQ line per
+// contig in file order (SN its name, LN its length), a row's RNAME is its contig's name and its POS counts from the
+// contig's start.
 struct SamContigs {
     const std::vector<FastaContig> *table;
-    const int32_t *row_contig;
+    const int32_t *row_contig; // indexed like the rows' ids
 };
-// `mapq` (DRM_SAM_MAPQ, null = "60" on every line): the MAPQ column of the block's rows, mapq[i * k + j] for row j of
-// query i; a row written unmapped prints 0.
-// `quals` (DRM_SAM_QUAL, null or empty = "*" in column 11): the quality line of every query, indexed like query_seqs;
-// it is printed reversed on a line whose SEQ is printed reverse-complemented.
-// `loci` (DRM_SAM_LOCI, with `aln` only): the rows of a query are its distinct loci (drm_hit_loci's slots, k = max_loci),
-// row 0 the primary; a query without rows is written as one unmapped line (flag 4), as under `ctg`. With `xa`
-// (DRM_SAM_XA) rows 1 .. get no line of their own: the primary line ends in the tag
+// What both writers need to know about a block. Row r of the block is one (query, window) pair: ids[r] its dense
+// window id, aln->rec[r] its alignment, mapq[r] its MAPQ, ctg->row_contig[r] its contig.
+struct SamBlock {
+    std::string path;
+    bool header = false;          // true: truncate and write @HD / @SQ first; false: append
+    std::string ref_name = "ref"; // @SQ SN / RNAME without contigs; LN is ref_len (the reference's quirk)
+    size_t ref_len = 0;           // the window length
+    const std::vector<std::string> *queries = nullptr;   // every query of the run, tagged ("<" read ">") or not
+    const std::vector<std::string> *query_ids = nullptr; // QNAME; a missing or empty one prints S1/<number>/0
+    // DRM_SAM_QUAL (null or empty = "*" in column 11): the quality line of every query, indexed like queries; printed
+    // reversed on a line whose SEQ is printed reverse-complemented
+    const std::vector<std::string> *quals = nullptr;
+    size_t q0 = 0;                      // the block's first query
+    const uint64_t *ids = nullptr;      // [rows]
+    const SamAlignments *aln = nullptr; // null (write_sam_block only): the reference's pseudo fields
+    const int32_t *mapq = nullptr;      // DRM_SAM_MAPQ (null = "60" on every line); a row written unmapped prints 0
+    const SamContigs *ctg = nullptr;    // with aln only; null = the one sequence ref_name
+};
+// The SAM lines of queries [q0, q0 + nq): query i has the rows i * k + j, j < counts[i]; row 0 is the primary, later
+// rows secondaries (flag 256). Without alignments a row prints the reference's pseudo fields
+//   QNAME FLAG ref <window's start + 1> 60 <read length>M * 0 0 SEQ QUAL       (SEQ and QUAL as read, also under flag 16)
+// `loci` (DRM_SAM_LOCI, with aln only): the rows of a query are its distinct loci (drm_hit_loci's slots, k = max_loci).
+// Under `loci` or contigs a query without rows is written as one unmapped line (flag 4). With `xa` (DRM_SAM_XA) rows
+// 1 .. get no line of their own: the primary line ends in the tag
 //   XA:Z:<RNAME>,<+|-><POS>,<CIGAR>,<NM>;...
 // one entry per such row that holds an alignment, POS 1-based in the contig's own coordinates, the sign the strand,
 // the CIGAR drm_sam_cigar's (drm_sam_cigar_region's over a flanked region); no tag when no entry remains.
-void write_sam_block(const std::string &path, bool header, const std::string &ref_name, size_t ref_len,
-                     const std::vector<std::string> &query_seqs, const std::vector<std::string> &query_ids,
-                     size_t q0, size_t nq, const uint64_t *ids, const int32_t *counts, size_t k,
-                     const SamAlignments *aln = nullptr, const int32_t *mapq = nullptr,
-                     const SamContigs *ctg = nullptr, const std::vector<std::string> *quals = nullptr,
-                     bool loci = false, bool xa = false);
+void write_sam_block(const SamBlock &b, size_t nq, const int32_t *counts, size_t k, bool loci = false,
+                     bool xa = false);
 // The alternates behind an XA:Z tag: those of block row r are ids[r * width + j] for first <= j < counts[r], with their
 // alignments aln->rec[r * width + j] and, under DRM_CONTIGS, their contigs ctg->row_contig[r * width + j].
 struct SamXa {
@@ -211,22 +240,20 @@ struct SamXa {
 };
 // The paired form (DRM_MATES, no reference counterpart): the two primary lines of pairs whose reads are queries
 // q0 + 2 * p (mate 1) and q0 + 2 * p + 1 (mate 2). Row r = 2 * p + m of the block carries the read's chosen window
-// ids[r] (counts[r] = 1, or 0 for a read without a hit) and its alignment aln.rec[r] as in the DRM_SAM_CIGAR mode
-// (one row per read); a read without a hit or with a status-1 record is unmapped. proper[p] != 0: drm_pair_hits
-// chose a proper combination. The fields that relate the two lines are drm_sam_pair_fields' (include/drm_hip.h):
+// (counts[r] = 1, or 0 for a read without a hit) and its alignment as in write_sam_block (b.aln is required); a read
+// without a hit or with a status-1 record is unmapped. proper[p] != 0: drm_pair_hits chose a proper combination. The
+// fields that relate the two lines are drm_sam_pair_fields' (include/drm_hip.h):
 //   mapped:   QNAME FLAG ref POS 60 CIGAR = PNEXT TLEN SEQ * AS:i:<score> NM:i:<nm>
 //   unmapped: QNAME FLAG ref|* POS 60 * =|* PNEXT TLEN SEQ *        (SEQ as read; "*" when neither mate is mapped)
-// `mapq` (null = "60"): mapq[r] for the line of row r; an unmapped mate prints 0.
-// `xa` (DRM_SAM_LOCI, null = no tag): the alternates of row r; a mapped mate's line ends in their XA:Z tag
-// (write_sam_block), and nothing else on the line changes.
-void write_sam_pairs(const std::string &path, bool header, const std::string &ref_name, size_t ref_len,
-                     const std::vector<std::string> &query_seqs, const std::vector<std::string> &query_ids,
-                     size_t q0, size_t npairs, const uint64_t *ids, const int32_t *counts, const int32_t *proper,
-                     const SamAlignments &aln, const int32_t *mapq = nullptr, const SamContigs *ctg = nullptr,
-                     const std::vector<std::string> *quals = nullptr, const SamXa *xa = nullptr);
+// Under contigs an unmapped mate takes its mate's RNAME and POS; mates on one contig print RNEXT "=", mates on two the
+// other's name and local PNEXT, TLEN 0 and never flag 0x2.
+// `xa` (DRM_SAM_LOCI, null = no tag): the alternates of row r; a mapped mate's line ends in their XA:Z tag, and nothing
+// else on the line changes.
+void write_sam_pairs(const SamBlock &b, size_t npairs, const int32_t *counts, const int32_t *proper,
+                     const SamXa *xa = nullptr);
 
 // Mate rescue (include/drm_hip.h, drm_mate_rescue): the region of one anchor id, the one statement of the rule that
-// the host entry points (formats.cpp) and the kernel (mate_rescue.hip) both compile. dlo / dhi are
+// the host entry points (read_rules.cpp) and the kernel (mate_rescue.hip) both compile. dlo / dhi are
 // max(0, min_tlen - ref_len) and max_tlen - ref_len.
 #if defined(__HIPCC__)
 #define DRM_HOST_DEVICE __host__ __device__
@@ -270,7 +297,7 @@ void check_rescue_params(const drm_pair_params *p, int64_t &dlo, int64_t &dhi);
 void check_scoring(const drm_sw_scoring *sc);
 
 // Mapping quality (include/drm_hip.h, drm_mapq_value): the one statement of the formula that the host entry points
-// (formats.cpp) and the kernels (mapq.hip) both compile. Arguments within [-2^20, 2^20]: 60 * 2^20 * 2^20 < 2^63.
+// (read_rules.cpp) and the kernels (mapq.hip) both compile. Arguments within [-2^20, 2^20]: 60 * 2^20 * 2^20 < 2^63.
 DRM_HOST_DEVICE inline int32_t mapq_value(int64_t s1, int64_t sub, int64_t n_sub, int64_t full, int64_t min_score)
 {
     if (s1 <= 0 || full <= 0)

@@ -94,7 +94,7 @@ extern "C" int drm_embed_kmer3_device(const uint8_t *d_rows, int64_t n, int32_t 
         if (e != hipSuccess)
             throw drm::Error(DRM_ERR_HIP, std::string("embed_rows_kernel launch: ") + hipGetErrorString(e));
         return DRM_OK;
-    } catch (const drm::Error &e) {
+    } catch (const drm::Error &e) { // not drm::guarded: only an Error becomes a code here, anything else leaves the call
         drm::set_last_error(e.what());
         return e.code;
     }

@@ -49,23 +49,6 @@ void abi_check(int rc)
         throw Error(rc, drm_last_error());
 }
 
-template <class F> int guard(F &&f)
-{
-    try {
-        f();
-        return DRM_OK;
-    } catch (const Error &e) {
-        drm::set_last_error(e.what());
-        return e.code;
-    } catch (const std::bad_alloc &) {
-        drm::set_last_error("out of host memory");
-        return DRM_ERR_ARG;
-    } catch (const std::exception &e) {
-        drm::set_last_error(e.what());
-        return DRM_ERR_ARG;
-    }
-}
-
 struct DevMem {
     void *p = nullptr;
     DevMem() = default;
@@ -513,7 +496,7 @@ extern "C" {
 
 int drm_host_alloc(void **ptr, size_t bytes)
 {
-    return guard([&] {
+    return drm::guarded([&] {
         if (!ptr)
             throw Error(DRM_ERR_ARG, "null argument");
         HC(hipHostMalloc(ptr, std::max<size_t>(bytes, 1), hipHostMallocDefault));
@@ -522,7 +505,7 @@ int drm_host_alloc(void **ptr, size_t bytes)
 
 int drm_host_free(void *ptr)
 {
-    return guard([&] {
+    return drm::guarded([&] {
         if (ptr)
             HC(hipHostFree(ptr));
     });
@@ -534,7 +517,7 @@ int drm_search_rerank_device(drm_index *index, drm_refs *refs, const float *d_x,
                              int32_t *d_nhops_upper, int32_t *d_sw_scores, uint64_t *d_sw_ids, int32_t *d_status,
                              void *stream, drm_pipeline_stats *stats)
 {
-    return guard([&] {
+    return drm::guarded([&] {
         search_rerank_device(index, refs, d_x, n, k_clusters, ef, d_queries, d_q_len, q_stride, stride, k, d_D, d_I,
                              d_ndis, d_nhops, d_nhops_upper, d_sw_scores, d_sw_ids, d_status, (hipStream_t)stream,
                              stats);
@@ -543,7 +526,7 @@ int drm_search_rerank_device(drm_index *index, drm_refs *refs, const float *d_x,
 
 int drm_search_rerank_prepare(drm_index *index, int64_t n, int32_t d, int32_t k_clusters, int32_t k, int32_t q_stride)
 {
-    return guard([&] {
+    return drm::guarded([&] {
         if (!index || n <= 0 || d <= 0 || k_clusters <= 0)
             throw Error(DRM_ERR_ARG, "invalid prepare arguments");
         drm_index_info info;
@@ -579,7 +562,7 @@ int drm_search_rerank(drm_index *index, drm_refs *refs, const float *x, int64_t 
                       int32_t k, float *D, int64_t *I, int32_t *sw_scores, uint64_t *sw_ids, int32_t *status,
                       drm_search_stats *stats)
 {
-    return guard([&] {
+    return drm::guarded([&] {
         search_rerank(index, refs, x, n, d, k_clusters, ef, queries, q_len, q_stride, stride, k, D, I, sw_scores,
                       sw_ids, status, stats);
     });
@@ -603,7 +586,7 @@ template <class F> void fan_out(int g, F &&f)
     std::vector<std::string> msg((size_t)g);
     for (int r = 0; r < g; ++r)
         th.emplace_back([&, r] {
-            try {
+            try { // not drm::guarded: code and message are kept per rank, and the caller reports the first
                 f(r);
             } catch (const Error &e) {
                 rc[(size_t)r] = e.code;
@@ -656,7 +639,7 @@ extern "C" {
 int drm_multi_create(const char *index_path, const int *devices, int ndev, const uint8_t *windows, int64_t n_ref,
                      int32_t ref_len, int64_t row_stride, drm_multi **out)
 {
-    return guard([&] {
+    return drm::guarded([&] {
         if (!index_path || !devices || !out || ndev <= 0)
             throw Error(DRM_ERR_ARG, "null argument or no device");
         *out = nullptr;
@@ -682,7 +665,7 @@ int drm_multi_create(const char *index_path, const int *devices, int ndev, const
 int drm_multi_create_genome(const char *index_path, const int *devices, int ndev, const uint8_t *genome, int64_t len,
                             int32_t ref_len, drm_multi **out)
 {
-    return guard([&] {
+    return drm::guarded([&] {
         if (!index_path || !devices || !out || ndev <= 0 || (!genome && len > 0))
             throw Error(DRM_ERR_ARG, "null argument or no device");
         *out = nullptr;
@@ -705,7 +688,7 @@ int drm_multi_create_genome(const char *index_path, const int *devices, int ndev
 
 int drm_multi_free(drm_multi *m)
 {
-    return guard([&] {
+    return drm::guarded([&] {
         if (!m)
             return;
         free_multi(m);
@@ -715,7 +698,7 @@ int drm_multi_free(drm_multi *m)
 
 int drm_multi_get_index_info(const drm_multi *m, drm_index_info *info)
 {
-    return guard([&] {
+    return drm::guarded([&] {
         if (!m || m->index.empty())
             throw Error(DRM_ERR_ARG, "null argument");
         abi_check(drm_index_get_info(m->index[0], info));
@@ -727,7 +710,7 @@ int drm_multi_search_rerank(drm_multi *m, const float *x, int64_t n, int32_t d, 
                             float *D, int64_t *I, int32_t *sw_scores, uint64_t *sw_ids, int32_t *status,
                             drm_search_stats *stats)
 {
-    return guard([&] {
+    return drm::guarded([&] {
         if (!m)
             throw Error(DRM_ERR_ARG, "null argument");
         if (n <= 0)
@@ -814,7 +797,7 @@ extern "C" {
 
 int drm_comm_unique_id(uint8_t *id)
 {
-    return guard([&] {
+    return drm::guarded([&] {
         if (!id)
             throw Error(DRM_ERR_ARG, "null argument");
         static_assert(sizeof(ncclUniqueId) == DRM_COMM_ID_BYTES, "RCCL unique id size");
@@ -826,7 +809,7 @@ int drm_comm_unique_id(uint8_t *id)
 
 int drm_comm_init(const uint8_t *id, int nranks, int rank, int device, drm_comm **out)
 {
-    return guard([&] {
+    return drm::guarded([&] {
         if (!id || !out || nranks < 1 || rank < 0 || rank >= nranks)
             throw Error(DRM_ERR_ARG, "invalid communicator arguments");
         *out = nullptr;
@@ -851,7 +834,7 @@ int drm_comm_init(const uint8_t *id, int nranks, int rank, int device, drm_comm 
 
 int drm_comm_free(drm_comm *c)
 {
-    return guard([&] {
+    return drm::guarded([&] {
         if (!c)
             return;
         if (c->comm)
@@ -863,7 +846,7 @@ int drm_comm_free(drm_comm *c)
 int drm_comm_gather_rows(drm_comm *c, const void *d_send, int64_t n_total, int64_t row_bytes, void *d_recv, int root,
                          void *stream)
 {
-    return guard([&] {
+    return drm::guarded([&] {
         if (!c || n_total < 0 || row_bytes <= 0 || root < 0 || root >= c->nranks)
             throw Error(DRM_ERR_ARG, "invalid gather arguments");
         if (c->rank == root && !d_recv)

@@ -57,6 +57,7 @@
 #include <functional>
 #include <iostream>
 #include <memory>
+#include <numeric>
 #include <sstream>
 #include <thread>
 
@@ -157,33 +158,43 @@ struct BlockAlignments {
         align_rows(rt, ids, cnt, m, k, queries, q_len, q_stride, ref_len, &bare, inside.data(), 2);
     }
 
+    // The two-pass rule of the alignment pass and of the MD pass over a list of np rows. launch(sub, n, stride, records,
+    // words) runs the n rows sub[0 .. n) of the list with `stride` words per row. Every row runs at 16 words first, in
+    // launches of at most 2^20 rows; the rows that come back with status 2 (more words than that) run again at `full`,
+    // the stride that cannot overflow; keep(p, record, words) then sees every row of the list in order, once.
+    template <class Rec, class Launch, class Keep>
+    static void two_pass(size_t np, int32_t full, Launch &&launch, Keep &&keep)
+    {
+        constexpr int32_t kStride = 16;
+        constexpr size_t kChunk = (size_t)1 << 20; // rows per launch
+        auto pass = [&](const std::vector<size_t> &sub, int32_t stride, std::vector<Rec> &r, std::vector<uint32_t> &w) {
+            r.resize(sub.size());
+            w.resize(sub.size() * (size_t)stride);
+            for (size_t c = 0; c < sub.size(); c += kChunk)
+                launch(sub.data() + c, std::min(kChunk, sub.size() - c), stride, r.data() + c,
+                       w.data() + c * (size_t)stride);
+        };
+        std::vector<size_t> all(np), again;
+        std::iota(all.begin(), all.end(), (size_t)0);
+        std::vector<Rec> r1, r2;
+        std::vector<uint32_t> w1, w2;
+        pass(all, kStride, r1, w1);
+        for (size_t p = 0; p < np; ++p)
+            if (r1[p].status == 2)
+                again.push_back(p);
+        pass(again, full, r2, w2);
+        for (size_t p = 0, x2 = 0; p < np; ++p) {
+            const bool retried = x2 < again.size() && again[x2] == p;
+            keep(p, retried ? r2[x2] : r1[p], retried ? w2.data() + x2 * (size_t)full : w1.data() + p * kStride);
+            x2 += retried;
+        }
+    }
+
     // the rows of the block whose pick[row] == want (pick null: every row), into rec / off / ops / the regions
     void align_rows(drm_refs *rt, const uint64_t *ids, const int32_t *cnt, size_t m, size_t k, const uint8_t *queries,
                     const int32_t *q_len, int32_t q_stride, int32_t ref_len, const AffineMode *affine,
                     const uint8_t *pick, uint8_t want = 0)
     {
-        constexpr int32_t kStride = 16;
-        constexpr size_t kChunk = (size_t)1 << 20; // pairs per launch
-        // one pass: the rows w against the queries q with `stride` operation words per row, into r and o
-        auto pass = [&](const std::vector<uint64_t> &w, const std::vector<int64_t> &q, int32_t stride,
-                        std::vector<drm_sw_alignment> &r, std::vector<uint32_t> &o) {
-            r.resize(w.size());
-            o.resize(w.size() * (size_t)stride);
-            for (size_t c = 0; c < w.size(); c += kChunk) {
-                const int64_t nc = (int64_t)std::min(kChunk, w.size() - c);
-                drm_sw_alignment *rc = r.data() + c;
-                uint32_t *oc = o.data() + c * (size_t)stride;
-                const drm_sw_clip clip{affine ? affine->clip : 0, 1, 1};
-                check(affine && affine->clip > 0
-                          ? drm_sw_align_affine_clip(rt, &affine->scoring, &clip, affine->flank, w.data() + c,
-                                                     q.data() + c, nc, queries, q_len, q_stride, (int64_t)m, rc, oc,
-                                                     stride)
-                      : affine ? drm_sw_align_affine(rt, &affine->scoring, affine->flank, w.data() + c, q.data() + c, nc,
-                                                     queries, q_len, q_stride, (int64_t)m, rc, oc, stride)
-                             : drm_sw_align(rt, w.data() + c, q.data() + c, nc, queries, q_len, q_stride, (int64_t)m, rc,
-                                            oc, stride));
-            }
-        };
         std::vector<uint64_t> wid;
         std::vector<int64_t> pq, row;
         for (size_t i = 0; i < m; ++i)
@@ -195,29 +206,36 @@ struct BlockAlignments {
                 row.push_back((int64_t)(i * k + j));
             }
         const size_t np = wid.size();
-        std::vector<drm_sw_alignment> r1, r2;
-        std::vector<uint32_t> o1, o2;
-        pass(wid, pq, kStride, r1, o1);
-        std::vector<uint64_t> wid2;
-        std::vector<int64_t> pq2, idx2;
-        for (size_t p = 0; p < np; ++p)
-            if (r1[p].status == 2) {
-                wid2.push_back(wid[p]);
-                pq2.push_back(pq[p]);
-                idx2.push_back((int64_t)p);
+        const int32_t flank = affine ? affine->flank : 0;
+        // the windows and queries of the rows sub[0 .. n), as the aligners take them
+        std::vector<uint64_t> w;
+        std::vector<int64_t> q;
+        auto gather = [&](const size_t *sub, size_t n) {
+            w.resize(n);
+            q.resize(n);
+            for (size_t x = 0; x < n; ++x) {
+                w[x] = wid[sub[x]];
+                q[x] = pq[sub[x]];
             }
-        const int32_t full = q_stride + ref_len + (affine ? 2 * affine->flank : 0);
-        pass(wid2, pq2, full, r2, o2);
-        size_t x2 = 0;
-        for (size_t p = 0; p < np; ++p) {
-            const bool retried = x2 < idx2.size() && idx2[x2] == (int64_t)p;
-            const drm_sw_alignment &r = retried ? r2[x2] : r1[p];
-            const uint32_t *o = retried ? o2.data() + x2 * (size_t)full : o1.data() + p * kStride;
-            x2 += retried;
-            rec[(size_t)row[p]] = r;
-            off[(size_t)row[p]] = (int64_t)ops.size();
-            ops.insert(ops.end(), o, o + r.n_ops);
-        }
+        };
+        two_pass<drm_sw_alignment>(
+            np, q_stride + ref_len + 2 * flank,
+            [&](const size_t *sub, size_t n, int32_t stride, drm_sw_alignment *rc, uint32_t *oc) {
+                gather(sub, n);
+                const drm_sw_clip clip{affine ? affine->clip : 0, 1, 1};
+                check(affine && affine->clip > 0
+                          ? drm_sw_align_affine_clip(rt, &affine->scoring, &clip, affine->flank, w.data(), q.data(),
+                                                     (int64_t)n, queries, q_len, q_stride, (int64_t)m, rc, oc, stride)
+                      : affine ? drm_sw_align_affine(rt, &affine->scoring, affine->flank, w.data(), q.data(), (int64_t)n,
+                                                     queries, q_len, q_stride, (int64_t)m, rc, oc, stride)
+                             : drm_sw_align(rt, w.data(), q.data(), (int64_t)n, queries, q_len, q_stride, (int64_t)m, rc,
+                                            oc, stride));
+            },
+            [&](size_t p, const drm_sw_alignment &r, const uint32_t *o) {
+                rec[(size_t)row[p]] = r;
+                off[(size_t)row[p]] = (int64_t)ops.size();
+                ops.insert(ops.end(), o, o + r.n_ops);
+            });
         if (affine) {
             for (size_t p = 0; p < np; ++p) {
                 int32_t rev = 0;
@@ -227,57 +245,31 @@ struct BlockAlignments {
         }
         if (!want_md)
             return;
-        // DRM_SAM_MD: the MD words of the rows just aligned, over the pass's own flank: 16 words per row first, then
-        // the rows that hold more (status 2) at the stride that cannot overflow
-        const int32_t flank = affine ? affine->flank : 0;
-        auto md_pass = [&](const std::vector<uint64_t> &w, const std::vector<int64_t> &q,
-                           const std::vector<drm_sw_alignment> &r, const std::vector<int64_t> &o, int32_t stride,
-                           std::vector<drm_sw_md> &h, std::vector<uint32_t> &words) {
-            h.resize(w.size());
-            words.resize(w.size() * (size_t)stride);
-            for (size_t c = 0; c < w.size(); c += kChunk) {
-                const int64_t nc = (int64_t)std::min(kChunk, w.size() - c);
-                check(drm_sw_align_md(rt, flank, w.data() + c, q.data() + c, nc, queries, q_len, q_stride, (int64_t)m,
-                                      r.data() + c, ops.data(), o.data() + c, h.data() + c,
-                                      words.data() + c * (size_t)stride, stride));
-            }
-        };
-        std::vector<drm_sw_alignment> mr(np), mr2;
-        std::vector<int64_t> mo(np), mo2;
-        for (size_t p = 0; p < np; ++p) {
-            mr[p] = rec[(size_t)row[p]];
-            mo[p] = off[(size_t)row[p]];
-        }
-        std::vector<drm_sw_md> h1, h2;
-        std::vector<uint32_t> w1, w2;
-        md_pass(wid, pq, mr, mo, kStride, h1, w1);
-        wid2.clear();
-        pq2.clear();
-        idx2.clear();
-        for (size_t p = 0; p < np; ++p)
-            if (h1[p].status == 2) {
-                wid2.push_back(wid[p]);
-                pq2.push_back(pq[p]);
-                mr2.push_back(mr[p]);
-                mo2.push_back(mo[p]);
-                idx2.push_back((int64_t)p);
-            }
-        const int32_t md_full = 2 * (ref_len + 2 * flank) + 1;
-        md_pass(wid2, pq2, mr2, mo2, md_full, h2, w2);
-        x2 = 0;
-        for (size_t p = 0; p < np; ++p) {
-            const bool retried = x2 < idx2.size() && idx2[x2] == (int64_t)p;
-            const drm_sw_md &h = retried ? h2[x2] : h1[p];
-            const uint32_t *w = retried ? w2.data() + x2 * (size_t)md_full : w1.data() + p * kStride;
-            x2 += retried;
-            // an aligner's own record and words always describe a walk; anything else is a fault of this program
-            if (h.status != 0 && h.status != 1)
-                throw drm::Error(DRM_ERR_ARG, "drm_sw_align_md: status " + std::to_string(h.status) + " on a row the "
-                                              "aligner produced");
-            md[(size_t)row[p]] = h;
-            md_off[(size_t)row[p]] = (int64_t)md_words.size();
-            md_words.insert(md_words.end(), w, w + h.n_words);
-        }
+        // DRM_SAM_MD: the MD words of the rows just aligned, over the pass's own flank
+        std::vector<drm_sw_alignment> r;
+        std::vector<int64_t> o;
+        two_pass<drm_sw_md>(
+            np, 2 * (ref_len + 2 * flank) + 1,
+            [&](const size_t *sub, size_t n, int32_t stride, drm_sw_md *h, uint32_t *words) {
+                gather(sub, n);
+                r.resize(n);
+                o.resize(n);
+                for (size_t x = 0; x < n; ++x) {
+                    r[x] = rec[(size_t)row[sub[x]]];
+                    o[x] = off[(size_t)row[sub[x]]];
+                }
+                check(drm_sw_align_md(rt, flank, w.data(), q.data(), (int64_t)n, queries, q_len, q_stride, (int64_t)m,
+                                      r.data(), ops.data(), o.data(), h, words, stride));
+            },
+            [&](size_t p, const drm_sw_md &h, const uint32_t *words) {
+                // an aligner's own record and words always describe a walk; anything else is a fault of this program
+                if (h.status != 0 && h.status != 1)
+                    throw drm::Error(DRM_ERR_ARG, "drm_sw_align_md: status " + std::to_string(h.status) + " on a row the "
+                                                  "aligner produced");
+                md[(size_t)row[p]] = h;
+                md_off[(size_t)row[p]] = (int64_t)md_words.size();
+                md_words.insert(md_words.end(), words, words + h.n_words);
+            });
     }
 };
 
@@ -931,6 +923,21 @@ struct Pipeline {
         std::filesystem::create_directories(o.out_dir);
     }
 
+    // What every block of the run's SAM file shares, for the block that starts at query q0 (the first one writes the
+    // header); the caller adds the block's rows.
+    drm::SamBlock sam_block(size_t q0) const
+    {
+        drm::SamBlock b;
+        b.path = o.sam_file;
+        b.header = q0 == 0;
+        b.ref_len = o.ref_len;
+        b.queries = &qseqs;
+        b.query_ids = &qids;
+        b.quals = &quals;
+        b.q0 = q0;
+        return b;
+    }
+
     // contig: with DRM_CONTIGS the contig of every row, indexed like ids (the flank guard)
     void align_block(BlockAlignments &ba, const uint64_t *ids, const int32_t *cnt, size_t lo, size_t m, size_t width,
                      const int32_t *contig = nullptr, bool md = true)
@@ -954,7 +961,7 @@ struct Pipeline {
         open_sam();
         const int rc = search(0, nq, &st);
         if (rc == DRM_OK && o.header_only)
-            drm::write_sam_block(o.sam_file, true, "ref", o.ref_len, qseqs, qids, 0, 0, nullptr, nullptr, k);
+            drm::write_sam_block(sam_block(0), 0, nullptr, k);
         else if (rc == DRM_OK)
             write_l2_rows();
         return rc;
@@ -998,8 +1005,10 @@ struct Pipeline {
                 align_block(ba, l2i.data() + lo * k, cnt.data() + lo, lo, m, k);
                 av = ba.view();
             }
-            drm::write_sam_block(o.sam_file, lo == 0, "ref", o.ref_len, qseqs, qids, lo, m, l2i.data() + lo * k,
-                                 cnt.data() + lo, k, o.sam_cigar ? &av : nullptr, nullptr, nullptr, &quals);
+            drm::SamBlock b = sam_block(lo);
+            b.ids = l2i.data() + lo * k;
+            b.aln = o.sam_cigar ? &av : nullptr;
+            drm::write_sam_block(b, m, cnt.data() + lo, k);
         }
     }
 
@@ -1311,9 +1320,13 @@ struct Pipeline {
             const drm::SamContigs sc{&ctable, contig->data()}, xsc{&ctable, xa_contig->data()};
             const drm::SamAlignments xav = xa_ba->view();
             const drm::SamXa xa{xa_ids->data(), xa_cnt->data(), na, 0, &xav, o.contigs ? &xsc : nullptr};
-            drm::write_sam_pairs(o.sam_file, lo == 0, "ref", o.ref_len, qseqs, qids, lo, mp, ids->data(), cnt->data(),
-                                 proper->data(), ba->view(), o.mapq ? line_mapq->data() : nullptr,
-                                 o.contigs ? &sc : nullptr, &quals, na ? &xa : nullptr);
+            const drm::SamAlignments av = ba->view();
+            drm::SamBlock b = sam_block(lo);
+            b.ids = ids->data();
+            b.aln = &av;
+            b.mapq = o.mapq ? line_mapq->data() : nullptr;
+            b.ctg = o.contigs ? &sc : nullptr;
+            drm::write_sam_pairs(b, mp, cnt->data(), proper->data(), na ? &xa : nullptr);
         };
     }
 
@@ -1375,8 +1388,12 @@ struct Pipeline {
         return [this, lo, m, n, ids, cnt, contig, ba, line_mapq] {
             const drm::SamAlignments av = ba->view();
             const drm::SamContigs sc{&ctable, contig->data()};
-            drm::write_sam_block(o.sam_file, lo == 0, "ref", o.ref_len, qseqs, qids, lo, m, ids->data(), cnt->data(), n,
-                                 &av, line_mapq->data(), o.contigs ? &sc : nullptr, &quals, true, o.sam_xa);
+            drm::SamBlock b = sam_block(lo);
+            b.ids = ids->data();
+            b.aln = &av;
+            b.mapq = line_mapq->data();
+            b.ctg = o.contigs ? &sc : nullptr;
+            drm::write_sam_block(b, m, cnt->data(), n, /*loci=*/true, o.sam_xa);
         };
     }
 
@@ -1413,9 +1430,12 @@ struct Pipeline {
         return [this, lo, m, kr, rows, cnt, ba, line_mapq] {
             const drm::SamAlignments av = ba->view();
             const drm::SamContigs sc{&ctable, o.contigs ? row_contig.data() + lo * k : nullptr};
-            drm::write_sam_block(o.sam_file, lo == 0, "ref", o.ref_len, qseqs, qids, lo, m, rows, cnt->data(), kr,
-                                 o.sam_cigar ? &av : nullptr, o.mapq ? line_mapq->data() : nullptr,
-                                 o.contigs ? &sc : nullptr, &quals);
+            drm::SamBlock b = sam_block(lo);
+            b.ids = rows;
+            b.aln = o.sam_cigar ? &av : nullptr;
+            b.mapq = o.mapq ? line_mapq->data() : nullptr;
+            b.ctg = o.contigs ? &sc : nullptr;
+            drm::write_sam_block(b, m, cnt->data(), kr);
         };
     }
 
