@@ -59,6 +59,8 @@ EXPORTS = [
     "drm_tlen_scan", "drm_tlen_scan_device", "drm_tlen_estimate",
     "drm_fasta_contigs", "drm_contigs_create", "drm_contigs_free", "drm_contigs_find", "drm_contig_lds_max",
     "drm_contig_hits", "drm_contig_hits_device",
+    "drm_sam_end5", "drm_dup_end_word", "drm_dup_slot", "drm_dupset_create", "drm_dupset_free", "drm_dupset_get_info",
+    "drm_dupset_mark", "drm_dupset_mark_device",
 ]
 
 
@@ -248,6 +250,14 @@ def lib():
         "drm_contig_lds_max": (C.c_int, []),
         "drm_contig_hits": (C.c_int, [vp, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp]),
         "drm_contig_hits_device": (C.c_int, [vp, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp]),
+        "drm_sam_end5": (C.c_int, [vp, i32, i64, i32, i32, C.POINTER(i64)]),
+        "drm_dup_end_word": (C.c_int, [i64, i32, C.POINTER(C.c_uint64)]),
+        "drm_dup_slot": (C.c_int, [C.c_uint64, C.c_uint64, i64, C.POINTER(i64)]),
+        "drm_dupset_create": (C.c_int, [i64, C.c_int, C.POINTER(vp)]),
+        "drm_dupset_free": (C.c_int, [vp]),
+        "drm_dupset_get_info": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
+        "drm_dupset_mark": (C.c_int, [vp, vp, i64, i64, vp]),
+        "drm_dupset_mark_device": (C.c_int, [vp, vp, i64, i64, vp, vp]),
         "drm_exact_search": (C.c_int, [vp, vp, i64, i32, i32, vp, vp, C.POINTER(C.c_double)]),
         "drm_exact_search_device": (C.c_int, [vp, vp, i64, i32, vp, vp, vp]),
         "drm_exact_search_l2": (C.c_int, [vp, i64, i32, vp, i64, i32, vp, vp, C.POINTER(C.c_double)]),

@@ -2614,6 +2614,127 @@ int drm_contig_hits(const drm_contigs *c, int32_t ref_len, const uint64_t *ids, 
     });
 }
 
+// ---------------------------------------------------------------------- duplicate set (dup_set.hip)
+struct drm_dupset {
+    int device = 0;
+    int64_t max_items = 0, slots = 0, next_item = 0;
+    uint64_t *keys = nullptr;            // [max_items][2]
+    unsigned long long *table = nullptr; // [slots]
+};
+
+int drm_dupset_create(int64_t max_items, int device, drm_dupset **out)
+{
+    return guarded([&] {
+        if (!out)
+            throw Error(DRM_ERR_ARG, "null argument");
+        if (device < 0)
+            throw Error(DRM_ERR_ARG, "negative device");
+        if (max_items < 1 || max_items > ((int64_t)1 << 31))
+            throw Error(DRM_ERR_ARG, "max_items " + std::to_string(max_items) + " outside [1, 2^31]");
+        std::unique_ptr<drm_dupset> s(new drm_dupset);
+        s->device = device;
+        s->max_items = max_items;
+        s->slots = 1;
+        while (s->slots < 2 * max_items)
+            s->slots *= 2;
+        DRM_HIP_CHECK(hipSetDevice(device));
+        DevBuf<uint64_t> keys(2 * (size_t)max_items);
+        DevBuf<unsigned long long> table((size_t)s->slots);
+        DRM_HIP_CHECK(hipMemset(table.p, 0, sizeof(unsigned long long) * (size_t)s->slots)); // every slot empty
+        DRM_HIP_CHECK(hipDeviceSynchronize());
+        s->keys = keys.p;
+        s->table = table.p;
+        keys.p = nullptr;
+        table.p = nullptr;
+        *out = s.release();
+    });
+}
+
+int drm_dupset_free(drm_dupset *s)
+{
+    return guarded([&] {
+        if (!s)
+            return;
+        (void)hipSetDevice(s->device);
+        (void)hipFree(s->keys);
+        (void)hipFree(s->table);
+        delete s;
+    });
+}
+
+int drm_dupset_get_info(const drm_dupset *s, int64_t *max_items, int64_t *slots, int64_t *next_item)
+{
+    return guarded([&] {
+        if (!s)
+            throw Error(DRM_ERR_ARG, "null duplicate set");
+        if (max_items)
+            *max_items = s->max_items;
+        if (slots)
+            *slots = s->slots;
+        if (next_item)
+            *next_item = s->next_item;
+    });
+}
+
+// every check of a mark call, before anything is touched; the kernels' arguments without the call's two arrays
+static drm::DupArgs make_dup_args(const drm_dupset *s, const uint64_t *ends, int64_t n, int64_t first_item,
+                                  const int64_t *first)
+{
+    if (!s)
+        throw Error(DRM_ERR_ARG, "null duplicate set");
+    if (n < 0)
+        throw Error(DRM_ERR_ARG, "n must be >= 0");
+    if (n > 0 && (!ends || !first))
+        throw Error(DRM_ERR_ARG, "null argument");
+    if (n > 0 && first_item < s->next_item)
+        throw Error(DRM_ERR_ARG, "first_item " + std::to_string(first_item) + " is below the set's next item " +
+                                     std::to_string(s->next_item) + ": items are marked in ascending order");
+    if (n > 0 && n > s->max_items - first_item)
+        throw Error(DRM_ERR_ARG, "items " + std::to_string(first_item) + " .. +" + std::to_string(n) +
+                                     " pass the set's max_items " + std::to_string(s->max_items));
+    drm::DupArgs a{};
+    a.keys = s->keys;
+    a.slots = s->table;
+    a.slot_mask = (uint64_t)s->slots - 1;
+    a.n = n;
+    a.first_item = first_item;
+    return a;
+}
+
+int drm_dupset_mark_device(drm_dupset *s, const uint64_t *d_ends, int64_t n, int64_t first_item, int64_t *d_first,
+                           void *stream)
+{
+    return guarded([&] {
+        drm::DupArgs a = make_dup_args(s, d_ends, n, first_item, d_first);
+        if (n == 0)
+            return;
+        DRM_HIP_CHECK(hipSetDevice(s->device));
+        a.ends = d_ends;
+        a.first = d_first;
+        drm::launch_dup_mark(a, (hipStream_t)stream);
+        s->next_item = first_item + n;
+    });
+}
+
+int drm_dupset_mark(drm_dupset *s, const uint64_t *ends, int64_t n, int64_t first_item, int64_t *first)
+{
+    return guarded([&] {
+        drm::DupArgs a = make_dup_args(s, ends, n, first_item, first);
+        if (n == 0)
+            return;
+        DRM_HIP_CHECK(hipSetDevice(s->device));
+        DevBuf<uint64_t> de(2 * (size_t)n);
+        DevBuf<int64_t> df((size_t)n);
+        de.upload(ends);
+        a.ends = de.p;
+        a.first = df.p;
+        drm::launch_dup_mark(a, nullptr);
+        s->next_item = first_item + n; // the items are in the table from here on, whatever the download does
+        DRM_HIP_CHECK(hipDeviceSynchronize());
+        df.download(first);
+    });
+}
+
 // ------------------------------------------------------------------------------- L2 rerank
 static drm::L2Args make_l2_args(drm_refs *refs, bool dynamic, const int64_t *nb, int64_t nq, int32_t kk,
                                 const float *qe, int32_t d, int64_t stride, int32_t k, int32_t k_clusters, float *td,

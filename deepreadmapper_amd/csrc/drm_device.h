@@ -465,6 +465,19 @@ struct ContigArgs {
 };
 void launch_contig_hits(ContigArgs a, hipStream_t stream);
 
+// First-seen duplicate set (dup_set.hip; drm_dupset_mark): one lane per item, the call's keys
+// written, inserted by linear probing with agent-scope atomics, then resolved to the smallest index of each key. Runs on
+// the current device; the entry points check first_item + n <= max_items before it is called.
+struct DupArgs {
+    uint64_t *keys;            // [max_items][2]: (lo, hi) of every item marked so far
+    unsigned long long *slots; // [slot_mask + 1]: 0 = empty, else item index + 1
+    uint64_t slot_mask;        // slots - 1, slots a power of two
+    const uint64_t *ends;      // [n][2] the call's end words
+    int64_t n, first_item;
+    int64_t *first;            // [n]
+};
+void launch_dup_mark(const DupArgs &a, hipStream_t stream);
+
 // L2 rerank (post_process_l2_static -> batch_reranker, src/utils/post_processor.cpp:1023-1162,
 // src/utils/reranker.cpp:98-195): distances from the window embedding table, libstdc++ partial_sort
 struct L2Args {

@@ -217,6 +217,9 @@ struct SamBlock {
     const SamAlignments *aln = nullptr; // null (write_sam_block only): the reference's pseudo fields
     const int32_t *mapq = nullptr;      // DRM_SAM_MAPQ (null = "60" on every line); a row written unmapped prints 0
     const SamContigs *ctg = nullptr;    // with aln only; null = the one sequence ref_name
+    // DRM_SAM_DUP (null = no line is marked): per query of the block, indexed from q0; a query with dup != 0 has 1024
+    // added to the flag of every line it prints (primary, secondary, unmapped); XA entries are untouched
+    const uint8_t *dup = nullptr;
 };
 // The SAM lines of queries [q0, q0 + nq): query i has the rows i * k + j, j < counts[i]; row 0 is the primary, later
 // rows secondaries (flag 256). Without alignments a row prints the reference's pseudo fields
@@ -312,6 +315,16 @@ DRM_HOST_DEVICE inline int32_t mapq_value(int64_t s1, int64_t sub, int64_t n_sub
 }
 // drm_mapq_params' accepted ranges (DRM_ERR_ARG)
 void check_mapq_params(const drm_mapq_params *p);
+
+// Duplicate set (include/drm_hip.h, drm_dupset): the slot hash of a key (lo, hi), the one statement that the kernels
+// (dup_set.hip) and drm_dup_slot compile: splitmix64's finaliser over lo ^ rotl(hi, 32); the slot is its low bits.
+DRM_HOST_DEVICE inline uint64_t dup_hash(uint64_t lo, uint64_t hi)
+{
+    uint64_t z = lo ^ ((hi << 32) | (hi >> 32));
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
 
 void build_hnswpq(const float *x, int64_t n, int d, int M_pq, int nbits, int M_hnsw, int efc, double sample_rate,
                   int nthreads, uint64_t seed, const std::string &path);

@@ -1,6 +1,7 @@
 // deepreadmapper_amd/csrc/read_rules.cpp -- the read-level rules that run on the host (include/drm_hip.h): the
 // accepted ranges of the pairing, rescue, scoring and MAPQ parameters, the mate rescue's window and choice, the MAPQ
-// formula's checked entry and the post-rescue MAPQ, and the template-length estimate.
+// formula's checked entry and the post-rescue MAPQ, the template-length estimate, and the duplicate marker's unclipped
+// 5' end, end word and slot hash.
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -289,5 +290,46 @@ extern "C" int drm_tlen_estimate(const uint32_t *hist_row, int32_t nbins, int32_
         if (min_samples < 1)
             throw drm::Error(DRM_ERR_ARG, "min_samples " + std::to_string(min_samples) + " must be >= 1");
         *out = tlen_estimate(hist_row, nbins, min_samples);
+    });
+}
+
+// ----------------------------------------------------------------------- duplicate marking: the host-only parts
+extern "C" int drm_sam_end5(const drm_sw_alignment *a, int32_t tag_prefix, int64_t region_start, int32_t region_len,
+                            int32_t reverse, int64_t *end5)
+{
+    using drm::Error;
+    return drm::guarded([&] {
+        if (!a || !end5)
+            throw Error(DRM_ERR_ARG, "null argument");
+        if (a->status != 0)
+            throw Error(DRM_ERR_ARG, "the record holds no complete alignment (status " + std::to_string(a->status) + ")");
+        const int64_t lead = (int64_t)a->q_begin - tag_prefix;
+        if (tag_prefix < 0 || lead < 0)
+            throw Error(DRM_ERR_ARG, "the alignment reaches into the query's prefix tag");
+        *end5 = reverse ? region_start + region_len - 1 - a->ref_begin + lead : region_start + a->ref_begin - lead;
+    });
+}
+
+extern "C" int drm_dup_end_word(int64_t end5, int32_t reverse, uint64_t *word)
+{
+    using drm::Error;
+    return drm::guarded([&] {
+        if (!word)
+            throw Error(DRM_ERR_ARG, "null argument");
+        if (end5 < -((int64_t)1 << 20) || end5 >= ((int64_t)1 << 61))
+            throw Error(DRM_ERR_ARG, "end5 " + std::to_string(end5) + " outside [-2^20, 2^61)");
+        *word = ((((uint64_t)(end5 + ((int64_t)1 << 20))) << 1) | (reverse != 0 ? 1u : 0u)) + 1;
+    });
+}
+
+extern "C" int drm_dup_slot(uint64_t lo, uint64_t hi, int64_t slots, int64_t *slot)
+{
+    using drm::Error;
+    return drm::guarded([&] {
+        if (!slot)
+            throw Error(DRM_ERR_ARG, "null argument");
+        if (slots < 1 || slots > ((int64_t)1 << 32) || (slots & (slots - 1)) != 0)
+            throw Error(DRM_ERR_ARG, "slots " + std::to_string(slots) + " is no power of two in [1, 2^32]");
+        *slot = (int64_t)(drm::dup_hash(lo, hi) & (uint64_t)(slots - 1));
     });
 }

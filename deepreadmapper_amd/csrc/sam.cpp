@@ -365,7 +365,8 @@ void drm::write_sam_block(const SamBlock &b, size_t nq, const int32_t *counts, s
         const std::string qname = qname_of(b, g, g + 1);
         SamLine unmapped; // the read without a row: the line's other columns stay "*" and 0
         unmapped.qname = qname;
-        unmapped.flag = 4;
+        const int dup = b.dup && b.dup[i] ? 1024 : 0; // DRM_SAM_DUP: on every line of the query
+        unmapped.flag = 4 | dup;
         unmapped.read = plain;
         unmapped.qual = qual_of(b, g);
         // DRM_SAM_XA: the rows behind the primary go into its XA:Z tag
@@ -374,7 +375,7 @@ void drm::write_sam_block(const SamBlock &b, size_t nq, const int32_t *counts, s
             const size_t row = i * k + (size_t)j;
             const uint64_t sid = b.ids[row];
             SamLine l = unmapped;
-            l.flag = (j == 0 ? 0 : 256) | (sid % 2 == 1 ? 16 : 0); // primary / secondary, reverse complement
+            l.flag = (j == 0 ? 0 : 256) | (sid % 2 == 1 ? 16 : 0) | dup; // primary / secondary, reverse complement
             Placed p; // real POS / CIGAR, SEQ on the forward strand; a hit without an alignment is written as unmapped
             if (b.aln) {
                 p = place_row(b.aln, row, sid, tagged, b.ref_len, contig_of(b.ctg, row));
@@ -436,7 +437,7 @@ void drm::write_sam_pairs(const SamBlock &b, size_t npairs, const int32_t *count
             const size_t row = 2 * pair + (size_t)m;
             SamLine l;
             l.qname = qname;
-            l.flag = f[m].flag;
+            l.flag = f[m].flag | (b.dup && b.dup[row] ? 1024 : 0); // DRM_SAM_DUP: the pair's answer on both lines
             if (f[m].has_rname) {
                 l.rname = *rname[m];
                 l.rnext = split ? std::string_view(*rname[1 - m]) : std::string_view("=");

@@ -874,6 +874,62 @@ int drm_contig_hits_device(const drm_contigs *c, int32_t ref_len, const uint64_t
                            uint64_t *d_out_spread, int32_t *d_out_scores, int32_t *d_out_contig, int32_t *d_out_cnt,
                            void *stream);
 
+/* ---------------------------------------------------------------- Duplicate marking (a first-seen set)
+ * A template (a read, or a pair) is a duplicate when an earlier template of the run has the same unclipped 5' ends on
+ * the same strands; the first one seen stays unmarked, as in samblaster. No sort is needed: the ends of every template
+ * so far live in a hash set on the device. The reference has no such step, so this text is the definition.
+ *
+ * drm_sam_end5 (host only): *end5 = the 0-based forward-strand coordinate under the read's first sequenced base, were
+ * its leading clip aligned without gaps. With lead = a->q_begin - tag_prefix:
+ *   forward (reverse == 0):  region_start + a->ref_begin - lead
+ *   reverse:                 region_start + region_len - 1 - a->ref_begin + lead
+ * the record being relative to the region genome[region_start ..+ region_len) as in drm_sam_cigar_region; for a window
+ * record (drm_sw_align) the region is (window_id / 2, ref_len, window_id & 1), as in drm_sam_cigar. It may be negative,
+ * by at most the query length. It is the unclipped 5' end that samtools or Picard derive from the printed line: forward,
+ * 1-based, POS minus the leading S; reverse, POS + reference span - 1 + the trailing S of the printed (reversed) CIGAR.
+ * Under a contig table the coordinate is that of the one genome string, so contigs need no key bits of their own; a
+ * clip that reaches past a contig's end is keyed where it would lie in that string.
+ * Examples: q_begin 4, tag_prefix 1, ref_begin 5, region (92, 166): forward 92 + 5 - 3 = 94; reverse 92 + 165 - 5 + 3 =
+ * 255. DRM_ERR_ARG: a null pointer, a->status != 0, tag_prefix < 0 or q_begin < tag_prefix (the alignment reaches into
+ * the prefix tag). */
+int drm_sam_end5(const drm_sw_alignment *a, int32_t tag_prefix, int64_t region_start, int32_t region_len,
+                 int32_t reverse, int64_t *end5);
+/* The end word of one mapped mate (host only): *word = (((uint64_t)(end5 + 2^20) << 1) | (reverse != 0)) + 1, for
+ * -2^20 <= end5 < 2^61 (DRM_ERR_ARG outside, or a null pointer). Word 0 means "this mate is unmapped".
+ * Examples: (0, 0) -> 2^21 + 1; (-2^20, 1) -> 2; (94, 1) -> ((2^20 + 94) << 1) + 2. */
+int drm_dup_end_word(int64_t end5, int32_t reverse, uint64_t *word);
+/* The key of an item with the end words (e1, e2) is the unordered pair lo = min(e1, e2), hi = max(e1, e2): which mate
+ * is mate 1 does not matter, F1R2 and F2R1 over the same ends are duplicates, as in Picard. A single read is the item
+ * (e, 0), and so is a pair with one unmapped mate. An item with hi == 0 has no key and is never a duplicate of anything.
+ *
+ * The set. Items are numbered over the whole run; a call marks items first_item .. first_item + n, where first_item must
+ * be >= the set's next_item (a gap is allowed) and first_item + n <= max_items; the call then sets next_item =
+ * first_item + n. first[i] is the smallest item index, over all calls so far including this one, that has item i's
+ * key, and -1 for an item without a key; item i is a duplicate iff 0 <= first[i] != first_item + i. Earlier calls hold
+ * smaller indices, so "smallest index" is "first seen", and the answers do not depend on how the run is cut into calls.
+ * n == 0 is DRM_OK and touches nothing. DRM_ERR_ARG, nothing touched: a null pointer (with n > 0), n < 0, first_item <
+ * next_item, first_item + n > max_items. Limits: 1 <= max_items <= 2^31.
+ * The handle owns keys[max_items] (16 bytes each: lo, hi) and slots, the smallest power of two >= 2 * max_items of
+ * 8 bytes each, a slot holding 0 or item index + 1: 32 to 48 bytes of device memory per item of capacity. The home slot
+ * of a key is
+ *   z = lo ^ rotl64(hi, 32); z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *   slot = (z ^ (z >> 31)) & (slots - 1)
+ * (splitmix64's finaliser) and a key lives in the first slot from there, wrapping at the end, that was empty when its
+ * first item arrived (linear probing). Results never depend on the hash; drm_dup_slot (host only)
+ * returns the home slot so that a test can restate the probing. slots must be a power of two in [1, 2^32].
+ * Like the other handles a set is single-stream: calls on one set must be serialised in stream order.
+ * drm_dupset_mark: host pointers, ends [n x 2], first [n]; runs on the set's device and returns when done.
+ * drm_dupset_mark_device: device pointers on the set's device, enqueued on `stream`; it makes the set's device the
+ * current one and leaves it so. */
+int drm_dup_slot(uint64_t lo, uint64_t hi, int64_t slots, int64_t *slot);
+typedef struct drm_dupset drm_dupset;
+int drm_dupset_create(int64_t max_items, int device, drm_dupset **out);
+int drm_dupset_free(drm_dupset *s);
+int drm_dupset_get_info(const drm_dupset *s, int64_t *max_items, int64_t *slots, int64_t *next_item);
+int drm_dupset_mark(drm_dupset *s, const uint64_t *ends, int64_t n, int64_t first_item, int64_t *first);
+int drm_dupset_mark_device(drm_dupset *s, const uint64_t *d_ends, int64_t n, int64_t first_item, int64_t *d_first,
+                           void *stream);
+
 /* ---------------------------------------------------------------- L2 rerank (the reference's live path)
  * post_process_l2_static (src/utils/post_processor.cpp:1023-1162, called at src/main.cpp:330) ->
  * find_sequences (static) -> Vectorizer::vectorize of the candidate windows -> batch_reranker(k = k_clusters)

@@ -42,6 +42,10 @@
 // written once, unmapped (flag 4). DRM_SAM_XA=1 beside it folds the alternatives into XA:Z:RNAME,<+|->POS,CIGAR,NM;...
 // at the end of the primary line. With DRM_MATES the alternatives of every mate whose line comes from a list row are
 // aligned in a second pass and appended as XA:Z; nothing else on a paired line changes.
+// DRM_SAM_DUP=1 (with DRM_SAM_CIGAR=1 and DRM_MATES or DRM_SAM_LOCI, the modes with one primary placement per read) marks
+// duplicate reads and pairs: every block hands the end words of its templates' unclipped 5' ends (drm_sam_end5,
+// drm_dup_end_word) to one first-seen set on the device (drm_dupset_mark), and every line of a template whose ends an
+// earlier template of the run had carries flag 1024.
 // DRM_SAM_STATS=1 prints the SAM stage's time and the rows it aligned.
 // DRM_SAM_QUAL=1 keeps the quality lines of .fastq / .fq queries (and DRM_MATES) and prints them in column 11, reversed
 // on a line whose SEQ is reverse-complemented; a quality line of another length than its read ends the run.
@@ -507,6 +511,7 @@ struct Options {
     bool sam_md = false;   // DRM_SAM_MD: MD:Z behind NM:i on every mapped line of the DRM_SAM_CIGAR modes
     bool sam_qual = false; // DRM_SAM_QUAL: column 11 from the FASTQ's quality lines
     bool sam_stats = false; // DRM_SAM_STATS: one line with the SAM stage's time and the rows it aligned
+    bool sam_dup = false;   // DRM_SAM_DUP: flag 1024 on the lines of a template whose 5' ends were seen before
     size_t sam_block = 0; // DRM_SAM_BLOCK, 0 = unset
 
     const AffineMode *affine() const { return has_affine ? &affine_mode : nullptr; }
@@ -592,6 +597,13 @@ static Options read_options(int argc, char *argv[], size_t ref_len, size_t strid
         throw drm::Error(DRM_ERR_ARG, "DRM_SAM_MD needs DRM_SAM_CIGAR=1: MD describes a real alignment");
     o.sam_qual = env_flag("DRM_SAM_QUAL");
     o.sam_stats = env_flag("DRM_SAM_STATS");
+    // DRM_SAM_DUP=0|1, parsed as strictly as DRM_SAM_XA; everything it needs is checked here, before the index is loaded
+    long dup_flag = 0;
+    env_range("DRM_SAM_DUP", 0, 1, dup_flag);
+    o.sam_dup = dup_flag != 0;
+    if (o.sam_dup && !(cigar && (o.paired || o.loci)))
+        throw drm::Error(DRM_ERR_ARG, "DRM_SAM_DUP needs DRM_SAM_CIGAR=1 with DRM_MATES or DRM_SAM_LOCI (and all they "
+                                      "need): a template is keyed by the one primary placement of each of its reads");
     if (const char *e = std::getenv("DRM_SAM_BLOCK"))
         o.sam_block = std::max<size_t>(1, std::strtoull(e, nullptr, 10));
     if (!o.is_npy)
@@ -703,6 +715,7 @@ struct Pipeline {
     std::vector<uint64_t> spread;
     std::vector<int32_t> row_contig;
     drm_pair_params pair_prm; // o.pair.prm, with DRM_PAIR_TLEN=auto the estimated window from estimate_tlen on
+    drm_dupset *dups = nullptr; // DRM_SAM_DUP: the run's first-seen set, one item per pair or read (run)
     // DRM_SAM_STATS: the rows handed to the aligner and the time of the blocks' produce steps (everything between the
     // rerank and the writer thread: the locus scans, the alignments, the MD pass)
     size_t aligned_rows = 0;
@@ -947,6 +960,37 @@ struct Pipeline {
             aligned_rows += (size_t)std::clamp<int64_t>(cnt[i], 0, (int64_t)width);
         ba.align(art, ids, cnt, m, width, qbuf.p + lo * qs, ql.p + lo, (int32_t)qs, (int32_t)o.ref_len, o.affine(),
                  contig ? ctg : nullptr, contig);
+    }
+
+    // DRM_SAM_DUP, after the alignment of a block: items [item0, item0 + n) of `per` reads each, block read r having its
+    // primary row at r * width of ids / ba and cnt[r] rows. A read whose primary row holds an alignment gives the end
+    // word of its unclipped 5' end, over the row's region when the block has regions, else over the window of its id; any
+    // other read gives 0. One drm_dupset_mark per block, the blocks being produced in item order; returns per read of the
+    // block whether its template is a duplicate.
+    std::shared_ptr<std::vector<uint8_t>> mark_duplicates(const BlockAlignments &ba, const uint64_t *ids,
+                                                          const int32_t *cnt, size_t lo, size_t item0, size_t n,
+                                                          size_t per, size_t width)
+    {
+        std::vector<uint64_t> ends(2 * n, 0);
+        const bool regions = !ba.region_start.empty();
+        for (size_t r = 0; r < n * per; ++r) {
+            const size_t row = r * width;
+            if (cnt[r] < 1 || ba.rec[row].status != 0)
+                continue;
+            const std::string &tagged = qseqs[lo + r];
+            const int32_t rev = (int32_t)(ids[row] & 1u);
+            int64_t end5 = 0;
+            check(drm_sam_end5(&ba.rec[row], !tagged.empty() && tagged.front() == '<',
+                               regions ? ba.region_start[row] : (int64_t)(ids[row] / 2),
+                               regions ? ba.region_len[row] : (int32_t)o.ref_len, rev, &end5));
+            check(drm_dup_end_word(end5, rev, &ends[2 * (r / per) + (per == 2 ? r % 2 : 0)]));
+        }
+        std::vector<int64_t> first(n, -1);
+        check(drm_dupset_mark(dups, ends.data(), (int64_t)n, (int64_t)item0, first.data()));
+        auto dup = std::make_shared<std::vector<uint8_t>>(n * per, 0);
+        for (size_t r = 0; r < n * per; ++r)
+            (*dup)[r] = first[r / per] >= 0 && first[r / per] != (int64_t)(item0 + r / per);
+        return dup;
     }
 
     // What the reference's sparse branch writes is only the SAM header: its write_sam_streaming call there
@@ -1289,6 +1333,8 @@ struct Pipeline {
             }
         }
         align_block(*ba, ids->data(), cnt->data(), lo, m, 1, o.contigs ? contig->data() : nullptr);
+        // DRM_SAM_DUP: one item per pair, a rescued mate keyed like any other mapped mate
+        const auto dup = o.sam_dup ? mark_duplicates(*ba, ids->data(), cnt->data(), lo, p0, mp, 2, 1) : nullptr;
         // DRM_SAM_LOCI: the loci of every list whose chosen row j_m became the mate's line (not a rescued or unmapped
         // mate), head = j_m; the alternates, slots 1 .., are aligned in a pass of their own and printed as XA:Z
         const size_t na = o.loci ? (size_t)o.loci_prm.max_loci - 1 : 0;
@@ -1316,7 +1362,7 @@ struct Pipeline {
                 }
             align_block(*xa_ba, xa_ids->data(), xa_cnt->data(), lo, m, na, o.contigs ? xa_contig->data() : nullptr, false);
         }
-        return [this, lo, mp, ids, cnt, proper, ba, line_mapq, contig, na, xa_ids, xa_cnt, xa_contig, xa_ba] {
+        return [this, lo, mp, ids, cnt, proper, ba, line_mapq, contig, na, xa_ids, xa_cnt, xa_contig, xa_ba, dup] {
             const drm::SamContigs sc{&ctable, contig->data()}, xsc{&ctable, xa_contig->data()};
             const drm::SamAlignments xav = xa_ba->view();
             const drm::SamXa xa{xa_ids->data(), xa_cnt->data(), na, 0, &xav, o.contigs ? &xsc : nullptr};
@@ -1326,6 +1372,7 @@ struct Pipeline {
             b.aln = &av;
             b.mapq = o.mapq ? line_mapq->data() : nullptr;
             b.ctg = o.contigs ? &sc : nullptr;
+            b.dup = dup ? dup->data() : nullptr;
             drm::write_sam_pairs(b, mp, cnt->data(), proper->data(), na ? &xa : nullptr);
         };
     }
@@ -1385,7 +1432,9 @@ struct Pipeline {
             }
         }
         align_block(*ba, ids->data(), cnt->data(), lo, m, n, o.contigs ? contig->data() : nullptr);
-        return [this, lo, m, n, ids, cnt, contig, ba, line_mapq] {
+        // DRM_SAM_DUP: one item per read, keyed by its primary locus (slot 0)
+        const auto dup = o.sam_dup ? mark_duplicates(*ba, ids->data(), cnt->data(), lo, lo, m, 1, n) : nullptr;
+        return [this, lo, m, n, ids, cnt, contig, ba, line_mapq, dup] {
             const drm::SamAlignments av = ba->view();
             const drm::SamContigs sc{&ctable, contig->data()};
             drm::SamBlock b = sam_block(lo);
@@ -1393,6 +1442,7 @@ struct Pipeline {
             b.aln = &av;
             b.mapq = line_mapq->data();
             b.ctg = o.contigs ? &sc : nullptr;
+            b.dup = dup ? dup->data() : nullptr;
             drm::write_sam_block(b, m, cnt->data(), n, /*loci=*/true, o.sam_xa);
         };
     }
@@ -1457,6 +1507,8 @@ struct Pipeline {
             return search(0, nq, &st);
         if (o.paired && o.pair.tlen_auto)
             estimate_tlen();
+        if (o.sam_dup) // after the estimate's sample run: the set sees the block loop's items only
+            check(drm_dupset_create((int64_t)std::max<size_t>(o.paired ? nq / 2 : nq, 1), device, &dups));
         open_sam(o.paired ? " (paired)" : "");
         const auto t0 = clk::now();
         const int rc =
@@ -1546,6 +1598,7 @@ int main(int argc, char *argv[])
         if (p.art != p.rt)
             drm_refs_free(p.art);
         drm_contigs_free(p.ctg);
+        drm_dupset_free(p.dups);
         drm_refs_free(p.rt); // the free calls take null
         drm_index_free(p.index);
         drm_multi_free(p.multi);
