@@ -1799,15 +1799,34 @@ static drm::AffineAlignArgs make_affine_args(const drm_refs *refs, const drm_sw_
     if (!refs || !sc)
         throw Error(DRM_ERR_ARG, "null refs / scoring");
     drm::check_scoring(sc);
-    if (flank < 0)
-        throw Error(DRM_ERR_ARG, "negative flank");
-    if (flank > 0 && !refs->dev.genome)
-        throw Error(DRM_ERR_ARG, "a flank needs a genome handle: a window table holds nothing beside its rows");
-    if ((int64_t)refs->dev.ref_len + 2 * (int64_t)flank > drm::kAlignMaxLen)
-        throw Error(DRM_ERR_UNSUPPORTED, "window length " + std::to_string(refs->dev.ref_len) + " + 2 * flank " +
-                                             std::to_string(flank) +
-                                             " > 256 is not supported by the GPU affine SW alignment kernel");
+    drm::check_align_flank("affine SW alignment", refs->dev.ref_len, flank, refs->dev.genome != nullptr);
     return drm::AffineAlignArgs{{}, sc->match, sc->mismatch, sc->gap_open, sc->gap_extend, flank, 0};
+}
+
+// the device and the host form of both affine entry points, from their filled arguments
+static void sw_align_affine_device(drm::AffineAlignArgs aa, drm_refs *refs, const uint64_t *d_window_ids,
+                                   const int64_t *d_pair_query, int64_t npairs, const uint8_t *d_queries,
+                                   const int32_t *d_q_len, int32_t q_stride, int64_t nq, drm_sw_alignment *d_out,
+                                   uint32_t *d_ops, int32_t ops_stride, void *stream)
+{
+    aa.base = make_align_args(refs, d_window_ids, d_pair_query, npairs, d_queries, d_q_len, q_stride, nq, d_out, d_ops,
+                              ops_stride);
+    if (npairs == 0)
+        return;
+    require_list_pointers(d_window_ids, d_pair_query, d_out, nq, d_queries, d_q_len, d_ops, ops_stride);
+    DRM_HIP_CHECK(hipSetDevice(refs->dev.device));
+    drm::launch_sw_align_affine(refs->dev, aa, q_stride, (hipStream_t)stream);
+}
+
+static void sw_align_affine_host(drm::AffineAlignArgs aa, drm_refs *refs, const uint64_t *window_ids,
+                                 const int64_t *pair_query, int64_t npairs, const uint8_t *queries, const int32_t *q_len,
+                                 int32_t q_stride, int64_t nq, drm_sw_alignment *out, uint32_t *ops, int32_t ops_stride)
+{
+    sw_align_host(refs, window_ids, pair_query, npairs, queries, q_len, q_stride, nq, out, ops, ops_stride,
+                  [&](const drm::AlignArgs &a, int max_q) {
+                      aa.base = a;
+                      drm::launch_sw_align_affine(refs->dev, aa, max_q, nullptr);
+                  });
 }
 
 int drm_sw_align_affine_device(drm_refs *refs, const drm_sw_scoring *scoring, int32_t flank,
@@ -1816,14 +1835,8 @@ int drm_sw_align_affine_device(drm_refs *refs, const drm_sw_scoring *scoring, in
                                drm_sw_alignment *d_out, uint32_t *d_ops, int32_t ops_stride, void *stream)
 {
     return guarded([&] {
-        drm::AffineAlignArgs aa = make_affine_args(refs, scoring, flank);
-        aa.base = make_align_args(refs, d_window_ids, d_pair_query, npairs, d_queries, d_q_len, q_stride, nq, d_out,
-                                  d_ops, ops_stride);
-        if (npairs == 0)
-            return;
-        require_list_pointers(d_window_ids, d_pair_query, d_out, nq, d_queries, d_q_len, d_ops, ops_stride);
-        DRM_HIP_CHECK(hipSetDevice(refs->dev.device));
-        drm::launch_sw_align_affine(refs->dev, aa, q_stride, (hipStream_t)stream);
+        sw_align_affine_device(make_affine_args(refs, scoring, flank), refs, d_window_ids, d_pair_query, npairs,
+                               d_queries, d_q_len, q_stride, nq, d_out, d_ops, ops_stride, stream);
     });
 }
 
@@ -1832,12 +1845,8 @@ int drm_sw_align_affine(drm_refs *refs, const drm_sw_scoring *scoring, int32_t f
                         int32_t q_stride, int64_t nq, drm_sw_alignment *out, uint32_t *ops, int32_t ops_stride)
 {
     return guarded([&] {
-        drm::AffineAlignArgs aa = make_affine_args(refs, scoring, flank);
-        sw_align_host(refs, window_ids, pair_query, npairs, queries, q_len, q_stride, nq, out, ops, ops_stride,
-                      [&](const drm::AlignArgs &a, int max_q) {
-                          aa.base = a;
-                          drm::launch_sw_align_affine(refs->dev, aa, max_q, nullptr);
-                      });
+        sw_align_affine_host(make_affine_args(refs, scoring, flank), refs, window_ids, pair_query, npairs, queries, q_len,
+                             q_stride, nq, out, ops, ops_stride);
     });
 }
 
@@ -1864,14 +1873,8 @@ int drm_sw_align_affine_clip_device(drm_refs *refs, const drm_sw_scoring *scorin
                                     void *stream)
 {
     return guarded([&] {
-        drm::AffineAlignArgs aa = make_affine_clip_args(refs, scoring, clip, flank);
-        aa.base = make_align_args(refs, d_window_ids, d_pair_query, npairs, d_queries, d_q_len, q_stride, nq, d_out,
-                                  d_ops, ops_stride);
-        if (npairs == 0)
-            return;
-        require_list_pointers(d_window_ids, d_pair_query, d_out, nq, d_queries, d_q_len, d_ops, ops_stride);
-        DRM_HIP_CHECK(hipSetDevice(refs->dev.device));
-        drm::launch_sw_align_affine(refs->dev, aa, q_stride, (hipStream_t)stream);
+        sw_align_affine_device(make_affine_clip_args(refs, scoring, clip, flank), refs, d_window_ids, d_pair_query,
+                               npairs, d_queries, d_q_len, q_stride, nq, d_out, d_ops, ops_stride, stream);
     });
 }
 
@@ -1881,12 +1884,8 @@ int drm_sw_align_affine_clip(drm_refs *refs, const drm_sw_scoring *scoring, cons
                              drm_sw_alignment *out, uint32_t *ops, int32_t ops_stride)
 {
     return guarded([&] {
-        drm::AffineAlignArgs aa = make_affine_clip_args(refs, scoring, clip, flank);
-        sw_align_host(refs, window_ids, pair_query, npairs, queries, q_len, q_stride, nq, out, ops, ops_stride,
-                      [&](const drm::AlignArgs &a, int max_q) {
-                          aa.base = a;
-                          drm::launch_sw_align_affine(refs->dev, aa, max_q, nullptr);
-                      });
+        sw_align_affine_host(make_affine_clip_args(refs, scoring, clip, flank), refs, window_ids, pair_query, npairs,
+                             queries, q_len, q_stride, nq, out, ops, ops_stride);
     });
 }
 
@@ -1898,13 +1897,9 @@ static drm::MdArgs make_md_args(const drm_refs *refs, int32_t flank, const uint6
 {
     if (!refs)
         throw Error(DRM_ERR_ARG, "null refs");
-    if (flank < 0 || md_stride < 0)
+    if (flank < 0 || md_stride < 0) // this entry's own wording, in front of the shared one
         throw Error(DRM_ERR_ARG, "negative flank / md_stride");
-    if (flank > 0 && !refs->dev.genome)
-        throw Error(DRM_ERR_ARG, "a flank needs a genome handle: a window table holds nothing beside its rows");
-    if ((int64_t)refs->dev.ref_len + 2 * (int64_t)flank > drm::kAlignMaxLen)
-        throw Error(DRM_ERR_UNSUPPORTED, "window length " + std::to_string(refs->dev.ref_len) + " + 2 * flank " +
-                                             std::to_string(flank) + " > 256 is not supported by the GPU MD kernel");
+    drm::check_align_flank("MD", refs->dev.ref_len, flank, refs->dev.genome != nullptr);
     return drm::MdArgs{make_align_args(refs, ids, pq, npairs, q, ql, q_stride, nq, nullptr, nullptr, 0),
                        flank, rec, ops, ops_off, out, md, md_stride};
 }
@@ -1988,20 +1983,11 @@ int drm_sw_align_region(const drm_refs *refs, uint64_t window_id, int32_t flank,
             throw Error(DRM_ERR_ARG, "null argument");
         if (!refs->dev.genome)
             throw Error(DRM_ERR_ARG, "drm_sw_align_region needs a genome handle");
-        if (flank < 0)
-            throw Error(DRM_ERR_ARG, "negative flank");
-        if ((int64_t)refs->dev.ref_len + 2 * (int64_t)flank > drm::kAlignMaxLen)
-            throw Error(DRM_ERR_UNSUPPORTED, "window length + 2 * flank > 256");
-        const uint64_t pos = window_id >> 1; // the twin of sw_align_affine_kernel's region (sw_align_affine.hip)
-        *reverse = (int32_t)(window_id & 1u);
-        *start = 0;
-        *len = 0;
-        if (pos + (uint64_t)refs->dev.ref_len > (uint64_t)refs->dev.glen)
-            return;
-        const int64_t s = std::max<int64_t>((int64_t)pos - flank, 0);
-        const int64_t e = std::min<int64_t>((int64_t)pos + refs->dev.ref_len + flank, refs->dev.glen);
-        *start = s;
-        *len = (int32_t)(e - s);
+        drm::check_align_flank(nullptr, refs->dev.ref_len, flank, true);
+        const drm::GenomeRegion r = drm::align_region(window_id, refs->dev.glen, refs->dev.ref_len, flank);
+        *start = r.start;
+        *len = r.len;
+        *reverse = r.reverse;
     });
 }
 

@@ -320,7 +320,6 @@ struct AlignArgs {
     uint32_t *ops;         // [npairs][ops_stride] BAM words, forward order
     int32_t ops_stride;
 };
-constexpr int kAlignMaxLen = 256; // longest query and window of the alignment kernel
 void launch_sw_align(const DeviceRefs &refs, AlignArgs a, int max_qlen, hipStream_t stream);
 
 // Affine-gap alignment over a flanked genome region (sw_align_affine.hip; drm_sw_align_affine):
@@ -338,7 +337,7 @@ struct AffineAlignArgs {
 void launch_sw_align_affine(const DeviceRefs &refs, AffineAlignArgs a, int max_qlen, hipStream_t stream);
 
 // The MD words of aligned pairs (sw_md.hip; drm_sw_align_md): one wave per pair walks the pair's
-// record and operation words over the region of (window id, flank) as the affine kernel cuts it and the query bytes.
+// record and operation words over the region of (window id, flank), the aligners' align_region, and the query bytes.
 // base holds the handle's windows, the pairs and the queries; its out / ops / ops_stride are not used.
 struct MdArgs {
     AlignArgs base;

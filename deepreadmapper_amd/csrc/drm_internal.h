@@ -255,22 +255,46 @@ struct SamXa {
 void write_sam_pairs(const SamBlock &b, size_t npairs, const int32_t *counts, const int32_t *proper,
                      const SamXa *xa = nullptr);
 
-// Mate rescue (include/drm_hip.h, drm_mate_rescue): the region of one anchor id, the one statement of the rule that
-// the host entry points (read_rules.cpp) and the kernel (mate_rescue.hip) both compile. dlo / dhi are
-// max(0, min_tlen - ref_len) and max_tlen - ref_len.
 #if defined(__HIPCC__)
 #define DRM_HOST_DEVICE __host__ __device__
 #else
 #define DRM_HOST_DEVICE
 #endif
-constexpr int kRescueMaxRows = 2048; // longest region: 11 bits of row in the kernel's best-cell key
-struct RescueRegion {
+// genome[start, start + len), read backwards and complemented when `reverse`; len 0 = no region
+struct GenomeRegion {
     int64_t start;
     int32_t len, reverse;
 };
-DRM_HOST_DEVICE inline RescueRegion rescue_region(uint64_t w, int64_t glen, int32_t ref_len, int64_t dlo, int64_t dhi)
+// The printed alignment (include/drm_hip.h, drm_sw_align_region): the region of one window id, its window widened by
+// `flank` bases on either side and clamped to the genome; none for a window that runs past the genome end. The one
+// statement of the rule that drm_sw_align_region (capi.cpp) and the kernels (sw_wave.h) both compile; at flank 0 it is
+// the window itself.
+constexpr int kAlignMaxLen = 256; // longest query and region of the alignment kernels
+DRM_HOST_DEVICE inline GenomeRegion align_region(uint64_t w, int64_t glen, int32_t ref_len, int32_t flank)
 {
-    RescueRegion r{0, 0, (int32_t)(1u - (uint32_t)(w & 1u))};
+    GenomeRegion r{0, 0, (int32_t)(w & 1u)};
+    const uint64_t pos = w >> 1;
+    if (pos + (uint64_t)ref_len > (uint64_t)glen)
+        return r;
+    const int64_t s = (int64_t)pos - flank, e = (int64_t)pos + ref_len + flank;
+    r.start = s > 0 ? s : 0;
+    r.len = (int32_t)((e < glen ? e : glen) - r.start);
+    return r;
+}
+// The aligners' limits, `what` naming the kernel in the message (null: drm_sw_align_region, which runs none). At
+// argument time: a flank is not negative and needs a genome handle (DRM_ERR_ARG), and the region fits the kernels
+// (DRM_ERR_UNSUPPORTED) ...
+void check_align_flank(const char *what, int32_t ref_len, int32_t flank, bool genome);
+// ... and at launch time, when the longest query is known: both sides within kAlignMaxLen (DRM_ERR_UNSUPPORTED)
+void check_align_launch(const char *what, int32_t ref_len, int32_t flank, int max_qlen);
+
+// Mate rescue (include/drm_hip.h, drm_mate_rescue): the region of one anchor id, the one statement of the rule that
+// the host entry points (read_rules.cpp) and the kernel (mate_rescue.hip) both compile. dlo / dhi are
+// max(0, min_tlen - ref_len) and max_tlen - ref_len.
+constexpr int kRescueMaxRows = 2048; // longest region: 11 bits of row in the kernel's best-cell key
+DRM_HOST_DEVICE inline GenomeRegion rescue_region(uint64_t w, int64_t glen, int32_t ref_len, int64_t dlo, int64_t dhi)
+{
+    GenomeRegion r{0, 0, (int32_t)(1u - (uint32_t)(w & 1u))};
     const uint64_t a = w >> 1;
     if (dhi < dlo || glen < 0 || a + (uint64_t)ref_len > (uint64_t)glen)
         return r;

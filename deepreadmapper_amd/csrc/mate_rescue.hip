@@ -14,19 +14,17 @@
 
 #include <algorithm>
 
-#include "drm_device.h"
+#include "sw_wave.h"
 
 namespace drm {
 namespace {
 
 constexpr int kNegInf = -(1 << 20); // the borders' E and F: below every real value, far from overflow
 
-// Best cell as one key, H << 19 | (2047 - row) << 8 | (63 - lane) << 2 | (3 - c): its maximum is the largest H, then
-// the smallest row, then the smallest column (a smaller column is a smaller lane, then a smaller c). H <= 31 * 256 <
-// 2^13, rows are 0-based and below 2^11.
-constexpr int kKeyHShift = 19, kKeyRowShift = 8;
-static_assert(kRescueMaxRows == 1 << (kKeyHShift - kKeyRowShift), "11 bits of row");
-static_assert(31 * kAlignMaxLen < 1 << (32 - kKeyHShift), "13 bits of score");
+// the best cell's key (sw_wave.h): H <= 31 * 256 < 2^13, rows are 0-based and below 2^11
+using RescueKey = CellKey<19, 0>;
+static_assert(kRescueMaxRows == RescueKey::kRowMax + 1, "11 bits of row");
+static_assert(31 * kAlignMaxLen < 1 << (32 - RescueKey::kHShift), "13 bits of score");
 
 template <int LQ>
 __global__ __launch_bounds__(64) void mate_rescue_kernel(RescueArgs a)
@@ -40,15 +38,10 @@ __global__ __launch_bounds__(64) void mate_rescue_kernel(RescueArgs a)
 
     for (int64_t p = blockIdx.x; p < a.ntasks; p += gridDim.x) {
         // ---- the task's region and query, the same on every lane
-        const RescueRegion rg = rescue_region(a.anchor_ids[p], a.glen, a.ref_len, a.dlo, a.dhi);
+        const GenomeRegion rg = rescue_region(a.anchor_ids[p], a.glen, a.ref_len, a.dlo, a.dhi);
         const int n = min(max(rg.len, 0), kRescueMaxRows);
-        const int64_t qi = a.task_query[p];
-        int m = 0;
-        const uint8_t *qp = a.queries;
-        if (qi >= 0 && qi < a.nq) {
-            m = min(max(a.q_len[qi], 0), min(a.q_stride, LQ));
-            qp = a.queries + qi * (int64_t)a.q_stride;
-        }
+        int m;
+        const uint8_t *qp = query_row(a, a.task_query[p], LQ, m);
         // rows run over the region as oriented: genome[start + r] forward, comp(genome[start + len - 1 - r]) reversed
         const uint8_t *gp = a.genome + rg.start + (rg.reverse ? rg.len - 1 : 0);
         const int dir = rg.reverse ? -1 : 1;
@@ -68,24 +61,19 @@ __global__ __launch_bounds__(64) void mate_rescue_kernel(RescueArgs a)
             qbuf[j] = qp[j];
         __syncthreads();
 
-        // ---- DP: H and F of the lane's C columns for the previous row in registers. -2 pads a column past the query:
-        //      it matches no byte, and such columns lie right of every real one, which never reads them. A padded cell
-        //      is some real cell's H minus at least its distance from it, so it never reaches the best score.
+        // ---- DP: H and F of the lane's C columns for the previous row in registers
         int qv[C], H[C], F[C];
         uint32_t cellkey[C];
+        column_setup<C>(qbuf, m, lane, qv, cellkey);
 #pragma unroll
         for (int c = 0; c < C; ++c) {
-            const int j0 = lane * C + c;
-            qv[c] = j0 < m ? (int)qbuf[j0] : -2;
             H[c] = 0;
             F[c] = kNegInf;
-            cellkey[c] = (uint32_t)(((63 - lane) << 2) | (3 - c));
         }
         // the left neighbour's last column: H of this row and of the row above, E of this row
         int left_cur = 0, left_prev = 0, left_e = kNegInf, e_last = kNegInf;
         uint32_t best = 0;
-        // the lane of the last real column finishes the last row at step n - 1 + (m - 1) / C
-        const int steps = (n > 0 && m > 0) ? n + (m - 1) / C : 0;
+        const int steps = skew_steps<C>(n, m);
         for (int t = 0; t < steps; ++t) {
             const int i0 = t - lane;
             if (i0 >= 0 && i0 < n) {
@@ -98,14 +86,14 @@ __global__ __launch_bounds__(64) void mate_rescue_kernel(RescueArgs a)
                     const int f = max(up - open_ext, F[c] - ext);
                     e = max(left - open_ext, e - ext);
                     const int h = max(max(max(diag + (wb == qv[c] ? match : -mismatch), f), e), 0);
-                    rowbest = max(rowbest, ((uint32_t)h << kKeyHShift) | cellkey[c]);
+                    rowbest = max(rowbest, ((uint32_t)h << RescueKey::kHShift) | cellkey[c]);
                     diag = up;
                     left = h;
                     H[c] = h;
                     F[c] = f;
                 }
                 e_last = e;
-                best = max(best, rowbest | ((uint32_t)(kRescueMaxRows - 1 - i0) << kKeyRowShift));
+                best = max(best, rowbest | RescueKey::row(i0));
             }
             // a lane that has not started yet still holds H = 0 and E = -inf: the borders above row 0; lane 0's left
             // neighbour is column 0, H = 0 and E = -inf on every row
@@ -113,19 +101,17 @@ __global__ __launch_bounds__(64) void mate_rescue_kernel(RescueArgs a)
             left_cur = shift_up1(0, H[C - 1]);
             left_e = shift_up1(kNegInf, e_last);
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1)
-            best = max(best, (uint32_t)__shfl_xor((int)best, off));
+        best = wave_max_u32(best);
 
         // ---- the record, the same on every lane
-        const int score = (int)(best >> kKeyHShift);
+        const int score = RescueKey::score(best);
         drm_rescue_result r;
         r.region_start = rg.start;
         r.region_len = rg.len;
         r.reverse = rg.reverse;
         r.score = score;
-        r.ref_end = score > 0 ? kRescueMaxRows - (int)((best >> kKeyRowShift) & (uint32_t)(kRescueMaxRows - 1)) : 0;
-        r.q_end = score > 0 ? (63 - (int)((best >> 2) & 63u)) * C + (3 - (int)(best & 3u)) + 1 : 0;
+        r.ref_end = score > 0 ? RescueKey::i_end(best) : 0;
+        r.q_end = score > 0 ? RescueKey::j_end<C>(best) : 0;
         r.status = score > 0 ? 0 : 1;
         if (lane == 0)
             a.out[p] = r;

@@ -45,6 +45,31 @@ void drm::check_scoring(const drm_sw_scoring *sc)
     range("gap_extend", sc->gap_extend, 1, 63);
 }
 
+void drm::check_align_flank(const char *what, int32_t ref_len, int32_t flank, bool genome)
+{
+    if (flank < 0)
+        throw Error(DRM_ERR_ARG, "negative flank");
+    if (flank > 0 && !genome)
+        throw Error(DRM_ERR_ARG, "a flank needs a genome handle: a window table holds nothing beside its rows");
+    if ((int64_t)ref_len + 2 * (int64_t)flank > kAlignMaxLen)
+        throw Error(DRM_ERR_UNSUPPORTED,
+                    what ? "window length " + std::to_string(ref_len) + " + 2 * flank " + std::to_string(flank) +
+                               " > 256 is not supported by the GPU " + what + " kernel"
+                         : std::string("window length + 2 * flank > 256"));
+}
+
+void drm::check_align_launch(const char *what, int32_t ref_len, int32_t flank, int max_qlen)
+{
+    const std::string tail = std::string(" > 256 is not supported by the GPU ") + what + " kernel";
+    if (max_qlen > kAlignMaxLen)
+        throw Error(DRM_ERR_UNSUPPORTED, "query length " + std::to_string(max_qlen) + tail);
+    const int64_t region = (int64_t)ref_len + 2 * (int64_t)flank;
+    if (region > kAlignMaxLen) // a kernel without a flank names its window alone
+        throw Error(DRM_ERR_UNSUPPORTED,
+                    "window length " + std::to_string(ref_len) +
+                        (flank ? " + 2 * flank " + std::to_string(flank) + " = " + std::to_string(region) : "") + tail);
+}
+
 static uint64_t rescue_window(const drm_rescue_result &r, int32_t ref_len, int64_t glen)
 {
     using drm::Error;
@@ -110,7 +135,7 @@ extern "C" int drm_mate_rescue_region(const drm_pair_params *p, int64_t glen, ui
             throw drm::Error(DRM_ERR_ARG, "negative genome length");
         int64_t dlo = 0, dhi = 0;
         drm::check_rescue_params(p, dlo, dhi);
-        const drm::RescueRegion r = drm::rescue_region(anchor_id, glen, p->ref_len, dlo, dhi);
+        const drm::GenomeRegion r = drm::rescue_region(anchor_id, glen, p->ref_len, dlo, dhi);
         *start = r.start;
         *len = r.len;
         *reverse = r.reverse;

@@ -14,7 +14,7 @@
 
 #include <algorithm>
 
-#include "drm_device.h"
+#include "sw_wave.h"
 
 namespace drm {
 namespace {
@@ -23,8 +23,6 @@ namespace {
 // 3 = "H is 0: the walk stops": the result's upper bits are 4 * H and its low two bits are the direction, with the
 // definition's order of preference (M, then D, then I) settled by the same maximum.
 enum : uint32_t { kDirI = 0, kDirD = 1, kDirM = 2, kDirStop = 3 };
-
-constexpr int kOpsWords = 2 * kAlignMaxLen; // a walk has at most n + m steps, so at most as many runs
 
 // LDS: ops[kOpsWords] u32 | window[256] | dirs[ref_len][64]
 constexpr size_t kAlignLdsFixed = sizeof(uint32_t) * kOpsWords + kAlignMaxLen;
@@ -41,51 +39,24 @@ __global__ __launch_bounds__(64) void sw_align_kernel(AlignArgs a)
     const int lane = threadIdx.x;
 
     for (int64_t p = blockIdx.x; p < a.npairs; p += gridDim.x) {
-        // ---- the pair's window (CandRow of sw_rerank.hip: table row, genome slice, reverse complement for odd
-        //      ids; an id outside the table / a window past the genome end is the empty string) and query
+        // ---- the pair's window (the region at flank 0) and query
         const uint64_t wid = a.window_ids[p];
-        const int64_t qi = a.pair_query[p];
-        const uint8_t *wp = nullptr;
-        int rc = 0;
-        if (a.genome) {
-            const uint64_t pos = wid >> 1;
-            if (pos + (uint64_t)a.ref_len <= (uint64_t)a.glen) {
-                rc = (int)(wid & 1u);
-                wp = a.genome + pos + (rc ? a.ref_len - 1 : 0);
-            }
-        } else if (wid < (uint64_t)a.n_ref) {
-            wp = a.refs + wid * (uint64_t)a.row_stride;
-        }
-        const int n = wp ? a.ref_len : 0;
-        int m = 0;
-        const uint8_t *qp = nullptr;
-        if (qi >= 0 && qi < a.nq) {
-            m = min(max(a.q_len[qi], 0), min(a.q_stride, LQ));
-            qp = a.queries + qi * (int64_t)a.q_stride;
-        }
+        const int64_t qi = a.pair_query[p]; // both indices are on their way before either is used
+        const WaveRegion rg = align_region(a, wid, 0);
+        const int n = rg.len;
+        int m;
+        const uint8_t *qp = query_row(a, qi, LQ, m);
         __syncthreads(); // the previous pair's traceback has read its LDS
-        for (int r = lane; r < n; r += 64)
-            wbuf[r] = (uint8_t)(rc ? comp_byte(wp[-r]) : (int)wp[r]);
+        stage_region(wbuf, rg, lane);
         __syncthreads();
 
-        // ---- DP: 4 * H of the lane's C columns for the previous row in registers. -2 pads a column past the query:
-        //      it matches no byte, and such columns lie right of every real one, which never reads them. A padded
-        //      cell is some real cell's H minus its distance from it, so it never reaches the best score either.
-        int qv[C], H4[C];
+        // ---- DP: 4 * H of the lane's C columns for the previous row in registers
+        int qv[C], H4[C] = {};
         uint32_t cellkey[C];
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const int j0 = lane * C + c;
-            qv[c] = j0 < m ? (int)qp[j0] : -2;
-            H4[c] = 0;
-            cellkey[c] = (uint32_t)(((63 - lane) << 2) | (3 - c)); // larger = further left
-        }
+        column_setup<C>(qp, m, lane, qv, cellkey);
         int left_cur = 0, left_prev = 0; // 4 * H of the left neighbour's last column: this row, the row above
-        // best cell as one key, H << 17 | (511 - row) << 8 | cellkey: max = (score descending, row ascending,
-        // column ascending)
-        uint32_t best = 0;
-        // the lane of the last real column finishes the last row at step n - 1 + (m - 1) / C
-        const int steps = (n > 0 && m > 0) ? n + (m - 1) / C : 0;
+        uint32_t best = 0;               // the best cell's AlignKey
+        const int steps = skew_steps<C>(n, m);
         for (int t = 0; t < steps; ++t) {
             const int i0 = t - lane;
             if (i0 >= 0 && i0 < n) {
@@ -100,29 +71,27 @@ __global__ __launch_bounds__(64) void sw_align_kernel(AlignArgs a)
                     const uint32_t k = (uint32_t)max(max(max(km, kd), ki), (int)kDirStop);
                     dbits |= (k & 3u) << (2 * c);
                     const uint32_t h4 = k & ~3u;
-                    rowbest = max(rowbest, (h4 << 15) | cellkey[c]);
+                    rowbest = max(rowbest, (h4 << (AlignKey::kHShift - 2)) | cellkey[c]);
                     diag = up;
                     left = (int)h4;
                     H4[c] = (int)h4;
                 }
-                best = max(best, rowbest | ((uint32_t)(510 - i0) << 8)); // 511 - (1-based row)
+                best = max(best, rowbest | AlignKey::row(i0));
                 dirs[i0 * 64 + lane] = (uint8_t)dbits;
             }
             // a lane that has not started yet still holds H = 0: the zero border above row 0
             left_prev = left_cur;
             left_cur = shift_up1(0, H4[C - 1]);
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1)
-            best = max(best, (uint32_t)__shfl_xor((int)best, off));
+        best = wave_max_u32(best);
         __syncthreads(); // every direction byte is in LDS
 
         // ---- traceback: every lane walks the same path (LDS broadcasts), so no lane-0 branch surrounds the loop
-        const int score = (int)(best >> 17);
-        const int i_end = score > 0 ? 511 - (int)((best >> 8) & 511u) : 0;
-        const int j_end = score > 0 ? (63 - (int)((best >> 2) & 63u)) * C + (3 - (int)(best & 3u)) + 1 : 0;
-        int i = i_end, j = j_end, nops = 0, n_m = 0, n_gap = 0;
-        uint32_t cur_op = 0, cur_len = 0;
+        const int score = AlignKey::score(best);
+        const int i_end = score > 0 ? AlignKey::i_end(best) : 0;
+        const int j_end = score > 0 ? AlignKey::j_end<C>(best) : 0;
+        int i = i_end, j = j_end, n_m = 0, n_gap = 0;
+        RunWriter runs{opsbuf};
         while (i > 0 && j > 0) {
             const int col = j - 1, ln = col / C, c = col - ln * C;
             const uint32_t d = ((uint32_t)dirs[(i - 1) * 64 + ln] >> (2 * c)) & 3u;
@@ -135,33 +104,13 @@ __global__ __launch_bounds__(64) void sw_align_kernel(AlignArgs a)
                 --i;
             if (d != kDirD)
                 --j;
-            if (cur_len > 0 && op != cur_op) {
-                opsbuf[nops++] = (cur_len << 4) | cur_op;
-                cur_len = 0;
-            }
-            cur_op = op;
-            ++cur_len;
+            runs.step(op);
         }
-        if (cur_len > 0)
-            opsbuf[nops++] = (cur_len << 4) | cur_op;
+        runs.finish();
         __syncthreads();
-        // the walk ran backwards: store the runs reversed
-        const int nstore = min(nops, a.ops_stride);
-        for (int x = lane; x < nstore; x += 64)
-            a.ops[p * (int64_t)a.ops_stride + x] = opsbuf[nops - 1 - x];
-        if (lane == 0) {
-            drm_sw_alignment r;
-            r.score = score;
-            r.ref_begin = i;
-            r.ref_end = i_end;
-            r.q_begin = j;
-            r.q_end = j_end;
-            // score = matches - mismatches - gap bases and n_m = matches + mismatches
-            r.nm = n_gap + (n_m - n_gap - score) / 2;
-            r.n_ops = nops;
-            r.status = score == 0 ? 1 : nops > a.ops_stride ? 2 : 0;
-            a.out[p] = r;
-        }
+        runs.store_reversed(a, p, lane);
+        // score = matches - mismatches - gap bases and n_m = matches + mismatches
+        store_alignment(a, p, lane, score, i, i_end, j, j_end, n_gap + (n_m - n_gap - score) / 2, runs.nops);
     }
 }
 
@@ -171,12 +120,7 @@ void launch_sw_align(const DeviceRefs &refs, AlignArgs a, int max_qlen, hipStrea
 {
     if (a.npairs <= 0)
         return;
-    if (max_qlen > kAlignMaxLen)
-        throw Error(DRM_ERR_UNSUPPORTED,
-                    "query length " + std::to_string(max_qlen) + " > 256 is not supported by the GPU SW alignment kernel");
-    if (refs.ref_len > kAlignMaxLen)
-        throw Error(DRM_ERR_UNSUPPORTED, "window length " + std::to_string(refs.ref_len) +
-                                             " > 256 is not supported by the GPU SW alignment kernel");
+    check_align_launch("SW alignment", refs.ref_len, 0, max_qlen);
     int cus = 0;
     DRM_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, refs.device));
     // bounded grid, each wave loops over pairs: 16 waves per CU (11.6 KB of LDS each at 150-byte windows)

@@ -20,7 +20,7 @@
 
 #include <algorithm>
 
-#include "drm_device.h"
+#include "sw_wave.h"
 
 namespace drm {
 namespace {
@@ -32,7 +32,6 @@ namespace {
 enum : uint32_t { kSrcE = 0, kSrcF = 1, kSrcM = 2, kSrcStop = 3, kFExt = 4, kEExt = 8 };
 
 constexpr int kNegInf = -(1 << 20); // the borders' E and F: below every real value, far from overflow, 0 mod 4
-constexpr int kOpsWords = 2 * kAlignMaxLen; // a walk has at most n + m steps, so at most as many runs
 
 // LDS: ops[kOpsWords] u32 | region[256] | query[256] | dirs[n][dir_lanes] u16
 constexpr size_t kAffineLdsFixed = sizeof(uint32_t) * kOpsWords + 2 * kAlignMaxLen;
@@ -60,66 +59,42 @@ __global__ __launch_bounds__(64) void sw_align_affine_kernel(AffineAlignArgs aa)
     const int tag_a = CLIP ? aa.tag_prefix : 0;
 
     for (int64_t p = blockIdx.x; p < a.npairs; p += gridDim.x) {
-        // ---- the pair's region: the table row, or genome[s, e) around the window, reverse-complemented as a whole for
-        //      odd ids; an id outside the table / a window past the genome end is the empty string
+        // ---- the pair's region and query
         const uint64_t wid = a.window_ids[p];
-        const int64_t qi = a.pair_query[p];
-        const uint8_t *wp = nullptr;
-        int rc = 0, n = 0;
-        if (a.genome) {
-            const uint64_t pos = wid >> 1; // the twin of drm_sw_align_region (capi.cpp)
-            if (pos + (uint64_t)a.ref_len <= (uint64_t)a.glen) {
-                const int64_t s = max((int64_t)pos - aa.flank, (int64_t)0);
-                const int64_t e = min((int64_t)pos + a.ref_len + aa.flank, a.glen);
-                n = min((int)(e - s), kAlignMaxLen);
-                rc = (int)(wid & 1u);
-                wp = a.genome + (rc ? e - 1 : s);
-            }
-        } else if (wid < (uint64_t)a.n_ref) {
-            wp = a.refs + wid * (uint64_t)a.row_stride;
-            n = min(a.ref_len, kAlignMaxLen);
-        }
-        int m = 0;
-        const uint8_t *qp = nullptr;
-        if (qi >= 0 && qi < a.nq) {
-            m = min(max(a.q_len[qi], 0), min(a.q_stride, LQ));
-            qp = a.queries + qi * (int64_t)a.q_stride;
-        }
+        const int64_t qi = a.pair_query[p]; // both indices are on their way before either is used
+        const WaveRegion rg = align_region(a, wid, aa.flank);
+        const int n = rg.len;
+        int m;
+        const uint8_t *qp = query_row(a, qi, LQ, m);
         const int tag_b = m - (CLIP ? aa.tag_postfix : 0);
         if (CLIP && tag_b < tag_a) // no read between the tags: no alignment
             m = 0;
         __syncthreads(); // the previous pair's traceback has read its LDS
-        for (int r = lane; r < n; r += 64)
-            wbuf[r] = (uint8_t)(rc ? comp_byte(wp[-r]) : (int)wp[r]);
+        stage_region(wbuf, rg, lane);
 
-        // ---- DP: 4 * H and 4 * F of the lane's C columns for the previous row in registers. -2 pads a column past the
-        //      query: it matches no byte, and such columns lie right of every real one, which never reads them. A
-        //      padded cell is some real cell's H minus at least its distance from it, so it never reaches the best score.
+        // ---- DP: 4 * H and 4 * F of the lane's C columns for the previous row in registers
         int qv[C], H4[C], F4[C];
         int stop4[C], end4[C]; // CLIP: 4 * floor(j) + 3, and 4 * kKeyBias less the column's end term
         uint32_t cellkey[C];
+        column_setup<C>(qp, m, lane, qv, cellkey);
 #pragma unroll
         for (int c = 0; c < C; ++c) {
             const int j0 = lane * C + c;
-            qv[c] = j0 < m ? (int)qp[j0] : -2;
             if (j0 < m)
                 qbuf[j0] = (uint8_t)qv[c];
             stop4[c] = CLIP && j0 >= tag_a ? (int)kSrcStop - clip4 : (int)kSrcStop; // column j0 + 1 > a
             end4[c] = 4 * kKeyBias - (j0 + 1 == tag_b ? 0 : clip4);
             H4[c] = stop4[c] - (int)kSrcStop; // row 0: H = floor(j)
             F4[c] = kNegInf;
-            cellkey[c] = (uint32_t)(((63 - lane) << 2) | (3 - c)); // larger = further left
         }
         __syncthreads();
         // the left neighbour's last column: 4 * H of this row and of the row above, 4 * E of this row
         // (rows 0 and -1 of the column left of the lane's first: its floor; column 0 is 0 on every row)
         const int left0 = CLIP && lane * C > tag_a ? -clip4 : 0;
         int left_cur = left0, left_prev = left0, left_e = kNegInf, e_last = kNegInf;
-        // best cell as one key, H << 17 | (511 - row) << 8 | cellkey: max = (score descending, row ascending,
-        // column ascending); H <= 31 * 256 < 2^13. CLIP: H less the end term plus kKeyBias, still < 2^13
+        // the best cell's AlignKey. CLIP: of H less the end term plus kKeyBias, still < 2^13
         uint32_t best = 0;
-        // the lane of the last real column finishes the last row at step n - 1 + (m - 1) / C
-        const int steps = (n > 0 && m > 0) ? n + (m - 1) / C : 0;
+        const int steps = skew_steps<C>(n, m);
         for (int t = 0; t < steps; ++t) {
             const int i0 = t - lane;
             if (i0 >= 0 && i0 < n) {
@@ -139,14 +114,14 @@ __global__ __launch_bounds__(64) void sw_align_affine_kernel(AffineAlignArgs aa)
                     // bit 0 of fk / ek set = opened: "extended" is its complement, at bits 2 and 3
                     dbits |= ((k & 3u) | ((uint32_t)(~fk & 1) << 2) | ((uint32_t)(~ek & 1) << 3)) << (4 * c);
                     const uint32_t h4 = k & ~3u;
-                    rowbest = max(rowbest, ((CLIP ? h4 + (uint32_t)end4[c] : h4) << 15) | cellkey[c]);
+                    rowbest = max(rowbest, ((CLIP ? h4 + (uint32_t)end4[c] : h4) << (AlignKey::kHShift - 2)) | cellkey[c]);
                     diag = up;
                     left = (int)h4;
                     H4[c] = (int)h4;
                     F4[c] = f;
                 }
                 e_last = e;
-                best = max(best, rowbest | ((uint32_t)(510 - i0) << 8)); // 511 - (1-based row)
+                best = max(best, rowbest | AlignKey::row(i0));
                 if (lane < dir_lanes) // the lanes past it hold padded columns only, which the walk never visits
                     dirs[i0 * dir_lanes + lane] = (uint16_t)dbits;
             }
@@ -156,19 +131,17 @@ __global__ __launch_bounds__(64) void sw_align_affine_kernel(AffineAlignArgs aa)
             left_cur = shift_up1(0, H4[C - 1]);
             left_e = shift_up1(kNegInf, e_last);
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1)
-            best = max(best, (uint32_t)__shfl_xor((int)best, off));
+        best = wave_max_u32(best);
         __syncthreads(); // every direction word is in LDS
 
         // ---- traceback: every lane walks the same path (LDS broadcasts), so no lane-0 branch surrounds the loop.
         //      state 0 = H, 1 = F (a run of region bytes, D), 2 = E (a run of query bytes, I)
-        const int adj = (int)(best >> 17) - kKeyBias; // the plain score; CLIP: less the end term (no cell: -128)
+        const int adj = AlignKey::score(best) - kKeyBias; // the plain score; CLIP: less the end term (no cell: -128)
         int score = CLIP ? max(adj, 0) : adj;
-        const int i_end = score > 0 ? 511 - (int)((best >> 8) & 511u) : 0;
-        const int j_end = score > 0 ? (63 - (int)((best >> 2) & 63u)) * C + (3 - (int)(best & 3u)) + 1 : 0;
-        int i = i_end, j = j_end, nops = 0, nm = 0, state = 0;
-        uint32_t cur_op = 0, cur_len = 0;
+        const int i_end = score > 0 ? AlignKey::i_end(best) : 0;
+        const int j_end = score > 0 ? AlignKey::j_end<C>(best) : 0;
+        int i = i_end, j = j_end, nm = 0, state = 0;
+        RunWriter runs{opsbuf};
         while (i > 0 && j > 0) {
             const int col = j - 1, ln = col / C, c = col - ln * C;
             const uint32_t d = ((uint32_t)dirs[(i - 1) * dir_lanes + ln] >> (4 * c)) & 15u;
@@ -197,34 +170,14 @@ __global__ __launch_bounds__(64) void sw_align_affine_kernel(AffineAlignArgs aa)
                 state = (d & kEExt) ? 2 : 0;
                 --j;
             }
-            if (cur_len > 0 && op != cur_op) {
-                opsbuf[nops++] = (cur_len << 4) | cur_op;
-                cur_len = 0;
-            }
-            cur_op = op;
-            ++cur_len;
+            runs.step(op);
         }
-        if (cur_len > 0)
-            opsbuf[nops++] = (cur_len << 4) | cur_op;
+        runs.finish();
         __syncthreads();
-        // the walk ran backwards: store the runs reversed
-        const int nstore = min(nops, a.ops_stride);
-        for (int x = lane; x < nstore; x += 64)
-            a.ops[p * (int64_t)a.ops_stride + x] = opsbuf[nops - 1 - x];
+        runs.store_reversed(a, p, lane);
         if (CLIP && score > 0) // the plain affine score of the walk: what it paid for its two ends comes back
             score += (j > tag_a ? clip4 / 4 : 0) + (j_end != tag_b ? clip4 / 4 : 0);
-        if (lane == 0) {
-            drm_sw_alignment r;
-            r.score = score;
-            r.ref_begin = i;
-            r.ref_end = i_end;
-            r.q_begin = j;
-            r.q_end = j_end;
-            r.nm = nm;
-            r.n_ops = nops;
-            r.status = score == 0 ? 1 : nops > a.ops_stride ? 2 : 0;
-            a.out[p] = r;
-        }
+        store_alignment(a, p, lane, score, i, i_end, j, j_end, nm, runs.nops);
     }
 }
 
@@ -235,13 +188,7 @@ void launch_sw_align_affine(const DeviceRefs &refs, AffineAlignArgs aa, int max_
     if (aa.base.npairs <= 0)
         return;
     const int region = refs.ref_len + 2 * aa.flank;
-    if (max_qlen > kAlignMaxLen)
-        throw Error(DRM_ERR_UNSUPPORTED, "query length " + std::to_string(max_qlen) +
-                                             " > 256 is not supported by the GPU affine SW alignment kernel");
-    if (region > kAlignMaxLen)
-        throw Error(DRM_ERR_UNSUPPORTED, "window length " + std::to_string(refs.ref_len) + " + 2 * flank " +
-                                             std::to_string(aa.flank) + " = " + std::to_string(region) +
-                                             " > 256 is not supported by the GPU affine SW alignment kernel");
+    check_align_launch("affine SW alignment", refs.ref_len, aa.flank, max_qlen);
     int cus = 0;
     DRM_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, refs.device));
     // one direction word per row for each lane that can hold a query column

@@ -19,7 +19,7 @@
 
 #include <algorithm>
 
-#include "drm_device.h"
+#include "sw_wave.h"
 
 namespace drm {
 namespace {
@@ -59,30 +59,13 @@ __global__ __launch_bounds__(64) void sw_md_kernel(MdArgs ma)
     const int lane = threadIdx.x;
 
     for (int64_t p = blockIdx.x; p < a.npairs; p += gridDim.x) {
-        // ---- the pair's region and query, as sw_align_affine_kernel cuts them
+        // ---- the pair's region and query
         const uint64_t wid = a.window_ids[p];
-        const int64_t qi = a.pair_query[p];
-        const uint8_t *wp = nullptr;
-        int rc = 0, n = 0;
-        if (a.genome) {
-            const uint64_t pos = wid >> 1;
-            if (pos + (uint64_t)a.ref_len <= (uint64_t)a.glen) {
-                const int64_t s = max((int64_t)pos - ma.flank, (int64_t)0);
-                const int64_t e = min((int64_t)pos + a.ref_len + ma.flank, a.glen);
-                n = min((int)(e - s), kAlignMaxLen);
-                rc = (int)(wid & 1u);
-                wp = a.genome + (rc ? e - 1 : s);
-            }
-        } else if (wid < (uint64_t)a.n_ref) {
-            wp = a.refs + wid * (uint64_t)a.row_stride;
-            n = min(a.ref_len, kAlignMaxLen);
-        }
-        int m = 0;
-        const uint8_t *qp = nullptr;
-        if (qi >= 0 && qi < a.nq) {
-            m = min(max(a.q_len[qi], 0), min(a.q_stride, kAlignMaxLen));
-            qp = a.queries + qi * (int64_t)a.q_stride;
-        }
+        const int64_t qi = a.pair_query[p]; // both indices are on their way before either is used
+        const WaveRegion rg = align_region(a, wid, ma.flank);
+        const int n = rg.len;
+        int m;
+        const uint8_t *qp = query_row(a, qi, kAlignMaxLen, m);
 
         // ---- what the record alone decides; every lane holds the same values
         const drm_sw_alignment r = ma.rec[p];
@@ -154,7 +137,7 @@ __global__ __launch_bounds__(64) void sw_md_kernel(MdArgs ma)
                 const uint32_t e = optab[lo];
                 const int rstart = (int)(e & 511u), qstart = (int)((e >> 9) & 511u);
                 const int ri = r.ref_begin + c; // < ref_end <= n
-                base[i] = rc ? comp_byte(wp[-ri]) : (int)wp[ri];
+                base[i] = rg.byte(ri);
                 if ((e >> 18) == 0u) {
                     const int qj = r.q_begin + qstart + (c - rstart); // < q_end <= m: the spans were checked
                     cls[i] = base[i] == (int)qp[qj] ? kMatch : kMismatch;
@@ -223,14 +206,7 @@ void launch_sw_md(const DeviceRefs &refs, const MdArgs &ma, int max_qlen, hipStr
 {
     if (ma.base.npairs <= 0)
         return;
-    const int region = refs.ref_len + 2 * ma.flank;
-    if (max_qlen > kAlignMaxLen)
-        throw Error(DRM_ERR_UNSUPPORTED,
-                    "query length " + std::to_string(max_qlen) + " > 256 is not supported by the GPU MD kernel");
-    if (region > kAlignMaxLen)
-        throw Error(DRM_ERR_UNSUPPORTED, "window length " + std::to_string(refs.ref_len) + " + 2 * flank " +
-                                             std::to_string(ma.flank) + " = " + std::to_string(region) +
-                                             " > 256 is not supported by the GPU MD kernel");
+    check_align_launch("MD", refs.ref_len, ma.flank, max_qlen);
     int cus = 0;
     DRM_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, refs.device));
     // the pass waits on memory, not on issue: 16 one-wave blocks a CU (4 per SIMD) to hide it, each looping over pairs

@@ -1,7 +1,8 @@
 """GPU tests of the affine-gap alignment over a flanked region (sw_align_affine.hip, drm_sw_align_affine): at
 {1, 1, 0, 1} and flank 0 it equals the linear kernel (drm_sw_align) word for word; under other scorings it equals
 the Python restatement of the definition (tests/sw_align_affine_ref.py) on every pair; the flank removes the clips
-that the window grid and indels cause; the device entry point and the DRM_SAM_SCORING / DRM_SAM_FLANK mode of
+that the window grid and indels cause; drm_sw_align_region and the affine, MD and linear kernels cut one region, and
+refuse one row more than 256 alike; the device entry point and the DRM_SAM_SCORING / DRM_SAM_FLANK mode of
 bin/pipeline agree with the host form."""
 import os
 import re
@@ -334,6 +335,64 @@ def test_flank_is_clamped_at_the_genome_ends(flank_genome):
             assert (pos1, cigar) == (pos + 1, "150M")
         else:
             assert int(rec["status"]) == 1
+    t.free()
+
+
+@pytest.mark.parametrize("flank", [0, 8, 53])  # 150 + 2 * 53 = 256 rows: the cap itself
+def test_host_and_device_cut_one_region(flank):
+    """drm_sw_align_region, the affine kernel, the MD kernel and (at flank 0) the linear kernel cut the same bytes: the
+    read is the region as the host entry gives it, so every kernel must see a full-length exact match of it. Windows
+    on both strands that the flank clamps at either genome end by all, one and none of its bases, and one it does not
+    clamp."""
+    from deepreadmapper_amd import GenomeTable, sw_align_affine_arrays, sw_align_arrays, sw_align_md_arrays, sw_align_region
+    ref_len, glen = 150, 600
+    g = _rand(np.random.default_rng(600), glen)
+    last = glen - ref_len
+    # 200 lies 53 bases from both ends: the one region of 256 rows; the last two positions hold no window
+    positions = [0, 7, 8, 200, last - 8, last - 7, last, last + 1, 2 ** 40]
+    ids = [2 * pos + strand for pos in positions for strand in (0, 1)]
+    t = GenomeTable(np.frombuffer(g, dtype=np.uint8), ref_len)
+    regions = [sw_align_region(t, w, flank) for w in ids]
+    for w, got in zip(ids, regions):  # the closed form
+        pos, start = w // 2, max(0, w // 2 - flank)
+        want = (start, min(glen, pos + ref_len + flank) - start, w % 2) if pos <= last else (0, 0, w % 2)
+        assert got == want, (w, flank)
+    reads = [(R.revcomp(g[s:s + n]) if rev else g[s:s + n]) if n else g[:ref_len] for s, n, rev in regions]
+    pq = np.arange(len(ids))
+    rec, ops = sw_align_affine_arrays(t, ids, pq, reads, FLANK_SCORING, flank=flank)
+    md, _ = sw_align_md_arrays(t, ids, pq, reads, rec, ops, flank=flank)
+    results = [(rec, md)]
+    if flank == 0:
+        lin = sw_align_arrays(t, ids, pq, reads)
+        aff = sw_align_affine_arrays(t, ids, pq, reads, LINEAR)
+        _same(aff, lin)
+        results.append((lin[0], sw_align_md_arrays(t, ids, pq, reads, *lin)[0]))
+    t.free()
+    for rec, md in results:
+        for p, (_, n, _) in enumerate(regions):
+            got = {f: int(rec[f][p]) for f in R.FIELDS}
+            if n == 0:
+                assert got["status"] == 1 and int(md["status"][p]) == 1, (p, flank)
+                continue
+            assert got == dict(score=n, ref_begin=0, ref_end=n, q_begin=0, q_end=n, nm=0, n_ops=1, status=0), (p, flank)
+            assert (int(md["n_match"][p]), int(md["n_mismatch"][p]), int(md["status"][p])) == (n, 0, 0), (p, flank)
+    assert [n for _, n, _ in regions[-4:]] == [0] * 4 and all(n > 0 for _, n, _ in regions[:-4])
+    assert flank != 53 or max(n for _, n, _ in regions) == 256
+
+
+def test_one_row_past_the_cap_is_refused_by_every_entry():
+    from deepreadmapper_amd import (DrmError, GenomeTable, sw_align_affine_arrays, sw_align_md_arrays,
+                                    sw_align_region)
+    from deepreadmapper_amd._native import DRM_ERR_UNSUPPORTED
+    g = _rand(np.random.default_rng(600), 600)
+    t = GenomeTable(np.frombuffer(g, dtype=np.uint8), 150)
+    rec, ops = sw_align_affine_arrays(t, [200], [0], [g[100:250]], FLANK_SCORING)
+    for call in (lambda: sw_align_affine_arrays(t, [200], [0], [g[100:250]], FLANK_SCORING, flank=54),
+                 lambda: sw_align_md_arrays(t, [200], [0], [g[100:250]], rec, ops, flank=54),
+                 lambda: sw_align_region(t, 200, 54)):  # 150 + 2 * 54 = 258 rows
+        with pytest.raises(DrmError) as e:
+            call()
+        assert e.value.code == DRM_ERR_UNSUPPORTED
     t.free()
 
 
