@@ -108,6 +108,7 @@ struct ReadBlock {
     size_t q0, nq, k;
     std::vector<int32_t> counts; // [nq]
     std::vector<Row> rows;       // [nq * k]
+    std::vector<uint8_t> dup;    // [nq], DRM_SAM_DUP; empty = the call passes none
 };
 struct PairBlock {
     size_t q0, npairs;
@@ -116,6 +117,7 @@ struct PairBlock {
     size_t xa_width = 0;                 // Mode::xa: the alternates of every row, from slot 0
     std::vector<int32_t> xa_counts;      // [2 * npairs]
     std::vector<Row> xa_rows;            // [2 * npairs * xa_width]
+    std::vector<uint8_t> dup;            // [2 * npairs], DRM_SAM_DUP; empty = the call passes none
 };
 
 const std::vector<drm::FastaContig> kContigs = {{"chrA", 0, 400}, {"chrB", 405, 600}};
@@ -139,7 +141,8 @@ drm::SamAlignments view(const Flat &f, const Mode &m)
 // ------------------------------------------------------------------------------------------ the two calls
 // what both calls say about a block
 drm::SamBlock block(const std::string &path, bool header, const Reads &r, size_t q0, const Flat &f, const Mode &m,
-                    size_t ref_len, const drm::SamAlignments *av, const drm::SamContigs *sc)
+                    size_t ref_len, const drm::SamAlignments *av, const drm::SamContigs *sc,
+                    const std::vector<uint8_t> &dup)
 {
     drm::SamBlock b;
     b.path = path;
@@ -153,6 +156,7 @@ drm::SamBlock block(const std::string &path, bool header, const Reads &r, size_t
     b.aln = m.aln ? av : nullptr;
     b.mapq = m.mapq ? f.mapq.data() : nullptr;
     b.ctg = m.contigs ? sc : nullptr;
+    b.dup = dup.empty() ? nullptr : dup.data();
     return b;
 }
 
@@ -162,8 +166,8 @@ void write_reads(const std::string &path, bool header, const Reads &r, const Rea
     const Flat f(b.rows);
     const drm::SamAlignments av = view(f, m);
     const drm::SamContigs sc{&kContigs, f.contig.data()};
-    drm::write_sam_block(block(path, header, r, b.q0, f, m, ref_len, &av, &sc), b.nq, b.counts.data(), b.k, m.loci,
-                         m.xa);
+    drm::write_sam_block(block(path, header, r, b.q0, f, m, ref_len, &av, &sc, b.dup), b.nq, b.counts.data(), b.k,
+                         m.loci, m.xa);
 }
 
 void write_pairs(const std::string &path, bool header, const Reads &r, const PairBlock &b, const Mode &m,
@@ -173,8 +177,8 @@ void write_pairs(const std::string &path, bool header, const Reads &r, const Pai
     const drm::SamAlignments av = view(f, m), xav = view(xf, m);
     const drm::SamContigs sc{&kContigs, f.contig.data()}, xsc{&kContigs, xf.contig.data()};
     const drm::SamXa xa{xf.ids.data(), b.xa_counts.data(), b.xa_width, 0, &xav, m.contigs ? &xsc : nullptr};
-    drm::write_sam_pairs(block(path, header, r, b.q0, f, m, ref_len, &av, &sc), b.npairs, b.counts.data(),
-                         b.proper.data(), m.xa ? &xa : nullptr);
+    drm::write_sam_pairs(block(path, header, r, b.q0, f, m, ref_len, &av, &sc, b.dup), b.npairs,
+                         b.counts.data(), b.proper.data(), m.xa ? &xa : nullptr);
 }
 
 // ------------------------------------------------------------------------------------------ single reads
@@ -273,6 +277,16 @@ std::vector<ReadBlock> loci_blocks()
               no_alignment(41, 5), rev, no_alignment(0), far, fwd, rev}}};
 }
 
+// DRM_SAM_DUP on reads 0, 2 and 4 (tests/test_sam_writer_cpu.py, DUP_READS): a read with a status-1 secondary and a
+// good one, a read without a locus, and a read whose primary holds no alignment
+std::vector<ReadBlock> loci_dup_blocks()
+{
+    std::vector<ReadBlock> b = loci_blocks();
+    b[0].dup = {1, 0, 1};
+    b[1].dup = {0, 1, 0};
+    return b;
+}
+
 // ------------------------------------------------------------------------------------------ pairs
 // six pairs; the reads of pair 5 have no id
 Reads pair_reads()
@@ -303,6 +317,16 @@ std::vector<PairBlock> pair_blocks()
                  no_alignment(41, 9), f160,              // pair 4: a counted row with a status-1 record
                  r150, untagged}};                       // pair 5: proper, the reverse mate first, no read ids
     return {a, b};
+}
+
+// DRM_SAM_DUP on pairs 0, 2 and 5 (DUP_PAIRS), the pair's answer on both of its rows: a proper pair, a pair with one
+// mate unmapped, and the pair without read ids
+std::vector<PairBlock> pair_dup_blocks()
+{
+    std::vector<PairBlock> b = pair_blocks();
+    b[0].dup = {1, 1, 0, 0, 1, 1};
+    b[1].dup = {0, 0, 0, 0, 1, 1};
+    return b;
 }
 
 // mates on two contigs (pair 0, called proper), on one contig (pairs 1 and 5), one mate unmapped beside chrB (pair 4)
@@ -476,9 +500,11 @@ int main(int argc, char **argv)
         case_reads(at("loci_xa"), loci_blocks(), m);
         m.xa = false;
         case_reads(at("loci"), loci_blocks(), m);
+        case_reads(at("loci_dup"), loci_dup_blocks(), m);
         m = Mode();
         m.aln = m.quals = true;
         case_pairs(at("pairs"), pair_blocks(), m);
+        case_pairs(at("pairs_dup"), pair_dup_blocks(), m);
         m.mapq = m.md = true;
         case_pairs(at("pairs_mapq"), pair_blocks(), m);
         m.md = false;

@@ -52,6 +52,28 @@ def test_every_case_is_recorded():
             "errors"} == set(CASES)
 
 
+DUP_READS = {"r0", "S1/3/0", "r4"}  # the driver's loci_dup: reads 0, 2 and 4 (reads 2 and 5 have no id of their own)
+DUP_PAIRS = {"p0", "p2", "S1/6/0"}  # pairs_dup: pairs 0, 2 and 5
+
+
+@pytest.mark.parametrize("case,base,names", [("loci_dup", "loci", DUP_READS), ("pairs_dup", "pairs", DUP_PAIRS)])
+def test_dup_adds_1024_to_every_line_of_the_chosen_reads(produced, case, base, names):
+    """The per-read `dup` field of a block: the file is the base case's recorded file with 1024 added to the flag of
+    every line -- primary, secondary, unmapped, both mates -- of the chosen reads, and nothing else changes."""
+    with open(os.path.join(GOLDEN, base + ".sam")) as f:
+        recorded = f.read().split("\n")
+    want, marked = [], set()
+    for line in recorded:
+        f = line.split("\t")
+        if not line.startswith("@") and f[0] in names:
+            assert not int(f[1]) & 1024
+            f[1] = str(int(f[1]) + 1024)
+            marked.add(f[0])
+        want.append("\t".join(f))
+    assert marked == names and any(int(x.split("\t")[1]) & 4 for x in want if x.split("\t")[0] in names)
+    assert (produced / (case + ".sam")).read_text().split("\n") == want
+
+
 @pytest.mark.parametrize("case", CASES)
 def test_sam_text_is_the_recorded_one(produced, case):
     path = produced / (case + ".sam")
