@@ -23,6 +23,8 @@ from .mapq import (MAPQ_RESULT_DTYPE, PAIR_MAPQ_RESULT_DTYPE, hit_mapq, hit_mapq
 from .loci import LOCI_DROP_DEFAULT, hit_loci, hit_loci_device, loci_params  # noqa: F401  (the locus list of a read)
 from .contigs import ContigTable, contig_hits, contig_hits_device, fasta_contigs  # noqa: F401  (multi-contig references)
 from .dups import DupSet, dup_end_word, dup_slot, sam_end5  # noqa: F401  (duplicate marking: a first-seen set)
+from .sorting import (sam_sort_key, sort_order, sort_order_device, sort_order_workspace, sort_scan_tiles,  # noqa: F401
+                      sort_tile)  # (coordinate order: a stable radix sort)
 
 __version__ = "0.4.0"
 from .executor import Comm, MultiIndex, search_rerank  # noqa: F401  (batch executor, multi-GPU, RCCL gather)

@@ -61,6 +61,8 @@ EXPORTS = [
     "drm_contig_hits", "drm_contig_hits_device",
     "drm_sam_end5", "drm_dup_end_word", "drm_dup_slot", "drm_dupset_create", "drm_dupset_free", "drm_dupset_get_info",
     "drm_dupset_mark", "drm_dupset_mark_device",
+    "drm_sam_sort_key", "drm_sort_tile", "drm_sort_scan_tiles", "drm_sort_order", "drm_sort_order_workspace",
+    "drm_sort_order_device",
 ]
 
 
@@ -258,6 +260,12 @@ def lib():
         "drm_dupset_get_info": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
         "drm_dupset_mark": (C.c_int, [vp, vp, i64, i64, vp]),
         "drm_dupset_mark_device": (C.c_int, [vp, vp, i64, i64, vp, vp]),
+        "drm_sam_sort_key": (C.c_int, [i64, i64, i32, C.POINTER(C.c_uint64)]),
+        "drm_sort_tile": (C.c_int, []),
+        "drm_sort_scan_tiles": (C.c_int, []),
+        "drm_sort_order": (C.c_int, [vp, i64, C.c_int, vp]),
+        "drm_sort_order_workspace": (C.c_int, [i64, C.POINTER(sz)]),
+        "drm_sort_order_device": (C.c_int, [vp, i64, vp, vp, sz, vp]),
         "drm_exact_search": (C.c_int, [vp, vp, i64, i32, i32, vp, vp, C.POINTER(C.c_double)]),
         "drm_exact_search_device": (C.c_int, [vp, vp, i64, i32, vp, vp, vp]),
         "drm_exact_search_l2": (C.c_int, [vp, i64, i32, vp, i64, i32, vp, vp, C.POINTER(C.c_double)]),

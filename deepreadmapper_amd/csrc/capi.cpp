@@ -2721,6 +2721,72 @@ int drm_dupset_mark(drm_dupset *s, const uint64_t *ends, int64_t n, int64_t firs
     });
 }
 
+// ---------------------------------------------------------------------- stable sort order (sort_order.hip)
+// every check of a sort call, before anything is touched; false when there is nothing to do
+static bool sort_checked(const void *keys, int64_t n, const void *order)
+{
+    if (n < 0)
+        throw Error(DRM_ERR_ARG, "n must be >= 0");
+    if (n == 0)
+        return false;
+    if (n >= ((int64_t)1 << 31))
+        throw Error(DRM_ERR_UNSUPPORTED, "n " + std::to_string(n) + " >= 2^31: the order is an array of 32-bit indices");
+    if (!keys || !order)
+        throw Error(DRM_ERR_ARG, "null argument");
+    return true;
+}
+
+// the launcher's workspace plus what aligning the caller's pointer to 256 bytes may cost
+static size_t sort_work_bytes(int64_t n) { return drm::sort_workspace_bytes(n) + 256; }
+
+int drm_sort_tile(void) { return drm::kSortTile; }
+int drm_sort_scan_tiles(void) { return drm::kSortScan; }
+
+int drm_sort_order_workspace(int64_t n, size_t *bytes)
+{
+    return guarded([&] {
+        if (!bytes)
+            throw Error(DRM_ERR_ARG, "null argument");
+        if (n < 0)
+            throw Error(DRM_ERR_ARG, "n must be >= 0");
+        if (n >= ((int64_t)1 << 31))
+            throw Error(DRM_ERR_UNSUPPORTED, "n " + std::to_string(n) + " >= 2^31");
+        *bytes = n == 0 ? 0 : sort_work_bytes(n);
+    });
+}
+
+int drm_sort_order_device(const uint64_t *d_keys, int64_t n, uint32_t *d_order, void *d_work, size_t work_bytes,
+                          void *stream)
+{
+    return guarded([&] {
+        if (!sort_checked(d_keys, n, d_order))
+            return;
+        if (!d_work || work_bytes < sort_work_bytes(n))
+            throw Error(DRM_ERR_ARG, "the workspace holds " + std::to_string(work_bytes) + " bytes, " +
+                                         std::to_string(sort_work_bytes(n)) + " are needed (drm_sort_order_workspace)");
+        void *aligned = reinterpret_cast<void *>(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
+        drm::launch_sort_order(d_keys, n, d_order, aligned, (hipStream_t)stream);
+    });
+}
+
+int drm_sort_order(const uint64_t *keys, int64_t n, int device, uint32_t *order)
+{
+    return guarded([&] {
+        if (!sort_checked(keys, n, order))
+            return;
+        if (device < 0)
+            throw Error(DRM_ERR_ARG, "negative device");
+        DRM_HIP_CHECK(hipSetDevice(device));
+        DevBuf<uint64_t> dk((size_t)n);
+        DevBuf<uint32_t> dord((size_t)n);
+        DevBuf<uint8_t> work(drm::sort_workspace_bytes(n)); // hipMalloc aligns to 256 bytes
+        dk.upload(keys);
+        drm::launch_sort_order(dk.p, n, dord.p, work.p, nullptr);
+        DRM_HIP_CHECK(hipDeviceSynchronize());
+        dord.download(order);
+    });
+}
+
 // ------------------------------------------------------------------------------- L2 rerank
 static drm::L2Args make_l2_args(drm_refs *refs, bool dynamic, const int64_t *nb, int64_t nq, int32_t kk,
                                 const float *qe, int32_t d, int64_t stride, int32_t k, int32_t k_clusters, float *td,

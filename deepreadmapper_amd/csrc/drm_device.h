@@ -477,6 +477,26 @@ struct DupArgs {
 };
 void launch_dup_mark(const DupArgs &a, hipStream_t stream);
 
+// Stable radix sort of 64-bit keys with their input indices as payload (sort_order.hip, DESIGN.md sec. 4.19;
+// drm_sort_order): eight 8-bit passes, least significant first, a pass whose byte is the same in every key (or tells
+// nothing but the all-ones keys from the rest, as a kept lower byte already does) skipped on the device. A tile is the kSortTile consecutive keys one block scatters: 4 waves of kSortRounds rounds of 64 keys. The
+// scan of a pass covers kSortScan tiles per step. Runs on the current device; the entry points check n < 2^31 and the
+// workspace before it is called.
+constexpr int kSortBlock = 256, kSortRounds = 16, kSortTile = kSortBlock * kSortRounds, kSortScan = 256;
+struct SortArgs {
+    const uint64_t *keys; // [n], never written
+    int64_t n, tiles;
+    uint32_t *hist;   // [8][256]: the keys per value of every byte; then one word, the all-ones keys
+    int32_t *plan;    // nine records of five words: what each pass reads and writes (sort_order.hip, PassPlan)
+    uint32_t *counts; // [256][tiles]: a pass's keys per value and tile, then their first destinations
+    uint64_t *k0, *k1; // [n] each: the keys between two passes
+    uint32_t *p0, *p1; // [n] each: the payloads between two passes; p0 is the caller's order
+};
+int64_t sort_tiles(int64_t n);
+size_t sort_workspace_bytes(int64_t n);
+// d_work holds sort_workspace_bytes(n) bytes, 256-byte aligned
+void launch_sort_order(const uint64_t *d_keys, int64_t n, uint32_t *d_order, void *d_work, hipStream_t stream);
+
 // L2 rerank (post_process_l2_static -> batch_reranker, src/utils/post_processor.cpp:1023-1162,
 // src/utils/reranker.cpp:98-195): distances from the window embedding table, libstdc++ partial_sort
 struct L2Args {

@@ -220,7 +220,20 @@ struct SamBlock {
     // DRM_SAM_DUP (null = no line is marked): per query of the block, indexed from q0; a query with dup != 0 has 1024
     // added to the flag of every line it prints (primary, secondary, unmapped); XA entries are untouched
     const uint8_t *dup = nullptr;
+    // DRM_SAM_SORT=coordinate (null = the lines go to the file): the writers touch no file; every line they build is
+    // appended to the spool instead, in the order in which it would have been written
+    struct SamSpool *spool = nullptr;
 };
+// The lines of a run held back until their order is known: line i is text[offsets[i] .. offsets[i + 1]) (the last one
+// to the end), newline included, and keys[i] its drm_sam_sort_key. All of it lives in host memory, a few hundred bytes
+// per line; a run whose lines do not fit needs an external merge, which this does not do.
+struct SamSpool {
+    std::string text;
+    std::vector<uint64_t> offsets, keys;
+};
+// The sorted file: @HD VN:1.0 SO:coordinate, b's @SQ lines (path, ref_name, ref_len and ctg->table are read), then line
+// order[i] of the spool for i = 0 .. The file is written beside b.path and renamed over it when complete.
+void write_sam_sorted(const SamBlock &b, const SamSpool &spool, const uint32_t *order);
 // The SAM lines of queries [q0, q0 + nq): query i has the rows i * k + j, j < counts[i]; row 0 is the primary, later
 // rows secondaries (flag 256). Without alignments a row prints the reference's pseudo fields
 //   QNAME FLAG ref <window's start + 1> 60 <read length>M * 0 0 SEQ QUAL       (SEQ and QUAL as read, also under flag 16)

@@ -1,10 +1,15 @@
 // deepreadmapper_amd/csrc/sam.cpp -- the SAM text: CIGAR / POS and MD of one GPU alignment record, the fields that
 // relate the two lines of a pair, and the writers of one block of reads or pairs (drm_internal.h, SamBlock).
 // Every line goes through SamLine / append_line, every row's POS and CIGAR through place_row.
+// DRM_SAM_SORT=coordinate: SamOut appends the lines to a SamSpool with their sort keys (drm_sam_sort_key) instead of
+// writing them, and write_sam_sorted writes the spool in a given order under @HD SO:coordinate. The spool holds the whole
+// run in host memory; an external merge for runs that do not fit is not implemented.
 #include <array>
+#include <cstdio>
 #include <cstring>
 #include <fstream>
 #include <string_view>
+#include <unordered_map>
 
 #include "drm_internal.h"
 
@@ -310,30 +315,75 @@ std::string qname_of(const SamBlock &b, size_t g, size_t number)
                                                                                 : "S1/" + std::to_string(number) + "/0";
 }
 
+// @HD with the given sort order, then @SQ: the reference's one line, or with a contig table one line per contig in
+// file order
+void write_header(std::ostream &out, const SamBlock &b, const char *order)
+{
+    out << "@HD\tVN:1.0\tSO:" << order << "\n";
+    if (!b.ctg)
+        out << "@SQ\tSN:" << b.ref_name << "\tLN:" << b.ref_len << "\n";
+    else
+        for (const FastaContig &c : *b.ctg->table)
+            out << "@SQ\tSN:" << c.name << "\tLN:" << c.len << "\n";
+}
+
+uint64_t sam_sort_key(int64_t tid, int64_t pos, bool reverse)
+{
+    if (tid == -1)
+        return ~0ull;
+    if (tid < 0 || tid >= ((int64_t)1 << 29))
+        throw Error(DRM_ERR_ARG, "tid " + std::to_string(tid) + " outside [-1, 2^29)");
+    if (pos < 0 || pos >= ((int64_t)1 << 33))
+        throw Error(DRM_ERR_ARG, "pos " + std::to_string(pos) + " outside [0, 2^33)");
+    return ((((uint64_t)tid << 33) | (uint64_t)pos) << 1) | (reverse ? 1u : 0u);
+}
+
 // The block's file: opened to truncate (with the header) or to append; the text is collected and written out whenever
 // it passes 4 MiB at the end of a record, and after the last one. A block that throws leaves the rest unwritten.
+// With a spool (DRM_SAM_SORT=coordinate) no file is touched: every line goes to the spool's text, with its offset and
+// its sort key (drm_sam_sort_key of the index of its RNAME among the @SQ lines, its POS and its flag's bit 16).
 class SamOut {
     std::ofstream out;
     std::string buf;
+    SamSpool *spool;
+    std::unordered_map<std::string_view, int64_t> tid; // spool only: RNAME -> its first @SQ line
 public:
-    explicit SamOut(const SamBlock &b) : out(b.path, b.header ? std::ios::out : std::ios::app)
+    explicit SamOut(const SamBlock &b) : spool(b.spool)
     {
+        if (spool) {
+            if (!b.ctg)
+                tid.emplace(b.ref_name, 0);
+            else
+                for (size_t i = 0; i < b.ctg->table->size(); ++i)
+                    tid.emplace((*b.ctg->table)[i].name, (int64_t)i);
+            return;
+        }
+        out.open(b.path, b.header ? std::ios::out : std::ios::app);
         if (!out.is_open())
             throw Error(DRM_ERR_IO, "Failed to open SAM file: " + b.path);
-        if (!b.header)
-            return;
-        // @HD, then @SQ: the reference's one line, or with a contig table one line per contig in file order
-        out << "@HD\tVN:1.0\tSO:unsorted\n";
-        if (!b.ctg)
-            out << "@SQ\tSN:" << b.ref_name << "\tLN:" << b.ref_len << "\n";
-        else
-            for (const FastaContig &c : *b.ctg->table)
-                out << "@SQ\tSN:" << c.name << "\tLN:" << c.len << "\n";
+        if (b.header)
+            write_header(out, b, "unsorted");
     }
-    void line(const SamLine &l) { append_line(buf, l); }
+    void line(const SamLine &l)
+    {
+        if (!spool) {
+            append_line(buf, l);
+            return;
+        }
+        int64_t t = -1;
+        if (l.rname != "*") {
+            const auto it = tid.find(l.rname);
+            if (it == tid.end())
+                throw Error(DRM_ERR_INTERNAL, "RNAME " + std::string(l.rname) + " is not in the header");
+            t = it->second;
+        }
+        spool->keys.push_back(sam_sort_key(t, l.pos, (l.flag & 16) != 0));
+        spool->offsets.push_back(spool->text.size());
+        append_line(spool->text, l);
+    }
     void end_record(bool last = false)
     {
-        if (!last && buf.size() <= (1u << 22))
+        if (spool || (!last && buf.size() <= (1u << 22)))
             return;
         out << buf;
         buf.clear();
@@ -458,4 +508,51 @@ void drm::write_sam_pairs(const SamBlock &b, size_t npairs, const int32_t *count
         out.end_record();
     }
     out.end_record(true);
+}
+
+// ----------------------------------------------------------------------- the coordinate-sorted file
+extern "C" int drm_sam_sort_key(int64_t tid, int64_t pos, int32_t reverse, uint64_t *key)
+{
+    return drm::guarded([&] {
+        if (!key)
+            throw Error(DRM_ERR_ARG, "null argument");
+        *key = sam_sort_key(tid, pos, reverse != 0);
+    });
+}
+
+void drm::write_sam_sorted(const SamBlock &b, const SamSpool &spool, const uint32_t *order)
+{
+    const size_t n = spool.keys.size();
+    if (spool.offsets.size() != n || (n > 0 && !order))
+        throw Error(DRM_ERR_ARG, "the spool's lines, keys and order do not match");
+    // written beside the file and renamed when complete: a run that fails here leaves no half-sorted results
+    const std::string part = b.path + ".part";
+    try {
+        std::ofstream out(part, std::ios::out | std::ios::trunc);
+        if (!out.is_open())
+            throw Error(DRM_ERR_IO, "Failed to open SAM file: " + part);
+        write_header(out, b, "coordinate");
+        std::string buf;
+        for (size_t i = 0; i < n; ++i) {
+            const size_t l = order[i];
+            if (l >= n)
+                throw Error(DRM_ERR_INTERNAL, "order[" + std::to_string(i) + "] = " + std::to_string(l) + " of " +
+                                                  std::to_string(n) + " lines");
+            const size_t from = spool.offsets[l], to = l + 1 < n ? spool.offsets[l + 1] : spool.text.size();
+            buf.append(spool.text, from, to - from);
+            if (buf.size() > (1u << 22)) {
+                out << buf;
+                buf.clear();
+            }
+        }
+        out << buf;
+        out.close();
+        if (!out)
+            throw Error(DRM_ERR_IO, "Failed to write SAM file: " + part);
+        if (std::rename(part.c_str(), b.path.c_str()) != 0)
+            throw Error(DRM_ERR_IO, "Failed to rename " + part + " to " + b.path);
+    } catch (...) {
+        std::remove(part.c_str());
+        throw;
+    }
 }

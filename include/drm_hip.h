@@ -930,6 +930,43 @@ int drm_dupset_mark(drm_dupset *s, const uint64_t *ends, int64_t n, int64_t firs
 int drm_dupset_mark_device(drm_dupset *s, const uint64_t *d_ends, int64_t n, int64_t first_item, int64_t *d_first,
                            void *stream);
 
+/* ---------------------------------------------------------------- Coordinate order (a stable GPU radix sort)
+ * bin/pipeline's DRM_SAM_SORT=coordinate writes the SAM lines in samtools sort's order: by the index of RNAME among the
+ * @SQ lines, then POS, then forward before reverse; lines whose RNAME is "*" last; lines of equal key in the order in
+ * which the unsorted file has them. The reference has no such step, so this text is the definition.
+ *
+ * drm_sam_sort_key (host only): the key of one line. tid = the index of the line's RNAME among the @SQ lines (0
+ * without a contig table), -1 for RNAME "*"; pos = the POS column as printed (1-based, 0 allowed); reverse = flag & 16.
+ *   tid == -1:  *key = 2^64 - 1
+ *   otherwise:  *key = (((uint64_t)tid << 33 | pos) << 1) | (reverse != 0),  0 <= tid < 2^29, 0 <= pos < 2^33
+ * DRM_ERR_ARG: a null pointer, tid < -1 or >= 2^29, pos < 0 or >= 2^33 (with tid == -1 pos and reverse are not looked
+ * at). The key is strictly increasing in (tid, pos, reverse) taken lexicographically, and 2^64 - 1 is above all of them.
+ * An unmapped mate that carries its mate's RNAME and POS gets that key and so sorts beside its mate; a secondary line
+ * sorts by its own position. Examples: (0, 1, 0) -> 2; (0, 1, 1) -> 3; (2, 100, 1) -> ((2 * 2^33 + 100) << 1) + 1. */
+int drm_sam_sort_key(int64_t tid, int64_t pos, int32_t reverse, uint64_t *key);
+/* The sort. order[i] = the input index of the key that comes i-th in ascending order; among equal keys the smaller
+ * index comes first (a stable sort: the result is the one permutation np.argsort(keys, kind="stable") gives, in every
+ * run). keys is not modified. n == 0 is DRM_OK before any device call; n >= 2^31 is DRM_ERR_UNSUPPORTED; n < 0, a null
+ * pointer with n > 0, a negative device, or (device form) a null or too small workspace is DRM_ERR_ARG; in all of these
+ * nothing is launched.
+ * A least-significant-digit radix sort over the keys' eight bytes with the index as 32-bit payload (DESIGN.md sec.
+ * 4.19): one pass over the keys counts every byte's values; a byte that is the same in every key costs nothing more,
+ * nor does a byte that only tells the all-ones keys from the rest when a lower byte does the same;
+ * every other byte costs a count, a scan and a scatter in which wave64 ballots place each key. No atomic decides a
+ * destination. drm_sort_tile returns the keys one block scatters (a tile), drm_sort_scan_tiles the tiles one step of
+ * the scan covers; both are there so that a test can aim at the boundaries.
+ * drm_sort_order: host arrays in and out; runs on `device` and returns when done.
+ * drm_sort_order_device: device memory on the current device, enqueued on `stream` (a hipStream_t, null = the default
+ * stream); nothing is copied back to the host in between, so the call returns before the sort ran. d_work is scratch
+ * memory of at least *bytes of drm_sort_order_workspace(n) (about 20 bytes per key, plus 1 KiB per tile); its content
+ * before and after the call means nothing. d_keys, d_order and d_work must not overlap. */
+int drm_sort_tile(void);
+int drm_sort_scan_tiles(void);
+int drm_sort_order(const uint64_t *keys, int64_t n, int device, uint32_t *order);
+int drm_sort_order_workspace(int64_t n, size_t *bytes);
+int drm_sort_order_device(const uint64_t *d_keys, int64_t n, uint32_t *d_order, void *d_work, size_t work_bytes,
+                          void *stream);
+
 /* ---------------------------------------------------------------- L2 rerank (the reference's live path)
  * post_process_l2_static (src/utils/post_processor.cpp:1023-1162, called at src/main.cpp:330) ->
  * find_sequences (static) -> Vectorizer::vectorize of the candidate windows -> batch_reranker(k = k_clusters)

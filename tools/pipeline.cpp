@@ -46,7 +46,15 @@
 // duplicate reads and pairs: every block hands the end words of its templates' unclipped 5' ends (drm_sam_end5,
 // drm_dup_end_word) to one first-seen set on the device (drm_dupset_mark), and every line of a template whose ends an
 // earlier template of the run had carries flag 1024.
-// DRM_SAM_STATS=1 prints the SAM stage's time and the rows it aligned.
+// DRM_SAM_SORT=coordinate (with use_dynamic=1 use_streaming=1 DRM_SAM_CIGAR=1, in every mode those allow; unsorted or
+// unset = the file as before, any other value is an error) writes the lines in samtools sort's order under
+// @HD SO:coordinate: the writers append every line to a spool in host memory with its key (drm_sam_sort_key of its
+// RNAME's @SQ index, POS and strand), and after the last block one stable GPU sort of the keys (drm_sort_order, DESIGN.md
+// sec. 4.19) gives the order in which the spool is written; lines of equal key keep the unsorted file's order, so the
+// file does not depend on DRM_SAM_BLOCK. The duplicate marks stay first-seen in input order. The spool holds the whole
+// run (a few hundred bytes per line); an external merge for runs that do not fit in host memory is not implemented.
+// DRM_SAM_STATS=1 prints the SAM stage's time and the rows it aligned, and with DRM_SAM_SORT the sort's and the final
+// write's time.
 // DRM_SAM_QUAL=1 keeps the quality lines of .fastq / .fq queries (and DRM_MATES) and prints them in column 11, reversed
 // on a line whose SEQ is reverse-complemented; a quality line of another length than its read ends the run.
 // Sequence inputs are embedded by the reference's GRU model on the GPU (drm_vectorize) when
@@ -512,6 +520,7 @@ struct Options {
     bool sam_qual = false; // DRM_SAM_QUAL: column 11 from the FASTQ's quality lines
     bool sam_stats = false; // DRM_SAM_STATS: one line with the SAM stage's time and the rows it aligned
     bool sam_dup = false;   // DRM_SAM_DUP: flag 1024 on the lines of a template whose 5' ends were seen before
+    bool sam_sort = false;  // DRM_SAM_SORT=coordinate: the lines are held back and written in coordinate order
     size_t sam_block = 0; // DRM_SAM_BLOCK, 0 = unset
 
     const AffineMode *affine() const { return has_affine ? &affine_mode : nullptr; }
@@ -606,6 +615,16 @@ static Options read_options(int argc, char *argv[], size_t ref_len, size_t strid
                                       "need): a template is keyed by the one primary placement of each of its reads");
     if (const char *e = std::getenv("DRM_SAM_BLOCK"))
         o.sam_block = std::max<size_t>(1, std::strtoull(e, nullptr, 10));
+    // DRM_SAM_SORT=unsorted|coordinate, nothing else; everything it needs is checked here, before the index is loaded
+    if (const char *e = std::getenv("DRM_SAM_SORT")) {
+        const std::string v = e;
+        if (v != "unsorted" && v != "coordinate")
+            throw drm::Error(DRM_ERR_ARG, "DRM_SAM_SORT must be unsorted or coordinate: " + quoted(v));
+        o.sam_sort = v == "coordinate";
+        if (o.sam_sort && !(use_dynamic && o.use_streaming && cigar && !o.is_npy))
+            throw drm::Error(DRM_ERR_ARG, "DRM_SAM_SORT=coordinate needs use_dynamic=1 use_streaming=1 DRM_SAM_CIGAR=1 "
+                                          "and sequence queries: the keys are the lines' real RNAME and POS");
+    }
     if (!o.is_npy)
         o.model = drm::encoder_model_path();
 
@@ -630,6 +649,9 @@ static Options read_options(int argc, char *argv[], size_t ref_len, size_t strid
     // alignment of the block's rows (drm_sw_align) before the host thread formats the block. Unset: no
     // alignment is launched and the file is the reference's.
     o.sam_cigar = o.stream_sam && !o.header_only && cigar;
+    if (o.sam_sort && (o.header_only || l2_rows))
+        throw drm::Error(DRM_ERR_ARG, "DRM_SAM_SORT=coordinate does not go with a sparse index's header-only SAM or "
+                                      "DRM_SAM_L2_ROWS=1: those files are not written by the block loop");
     return o;
 }
 
@@ -716,6 +738,8 @@ struct Pipeline {
     std::vector<int32_t> row_contig;
     drm_pair_params pair_prm; // o.pair.prm, with DRM_PAIR_TLEN=auto the estimated window from estimate_tlen on
     drm_dupset *dups = nullptr; // DRM_SAM_DUP: the run's first-seen set, one item per pair or read (run)
+    // DRM_SAM_SORT=coordinate: every line of the run with its key, filled by the writer thread block after block
+    mutable drm::SamSpool spool;
     // DRM_SAM_STATS: the rows handed to the aligner and the time of the blocks' produce steps (everything between the
     // rerank and the writer thread: the locus scans, the alignments, the MD pass)
     size_t aligned_rows = 0;
@@ -948,6 +972,7 @@ struct Pipeline {
         b.query_ids = &qids;
         b.quals = &quals;
         b.q0 = q0;
+        b.spool = o.sam_sort ? &spool : nullptr;
         return b;
     }
 
@@ -1489,6 +1514,27 @@ struct Pipeline {
         };
     }
 
+    // DRM_SAM_SORT=coordinate, after the last block: one drm_sort_order over the keys of every spooled line, then the
+    // header and the lines in that order. Equal keys keep the order of the unsorted file, so the result does not depend
+    // on DRM_SAM_BLOCK.
+    void write_sorted_sam()
+    {
+        const size_t n = spool.keys.size();
+        std::vector<uint32_t> order(n);
+        auto t0 = clk::now();
+        check(drm_sort_order(spool.keys.data(), (int64_t)n, device, order.data()));
+        const double sort_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+        t0 = clk::now();
+        const drm::SamContigs sc{&ctable, nullptr};
+        drm::SamBlock b = sam_block(0);
+        b.ctg = o.contigs ? &sc : nullptr;
+        drm::write_sam_sorted(b, spool, order.data());
+        if (o.sam_stats)
+            std::cout << "[MAIN] SAM sort: " << n << " lines, " << sort_ms << " ms for the order (copies included), "
+                      << std::chrono::duration<double, std::milli>(clk::now() - t0).count()
+                      << " ms for the final write" << std::endl;
+    }
+
     // the search + rerank and, with use_streaming, the SAM of the chosen output mode; returns the search's code
     int run()
     {
@@ -1521,6 +1567,8 @@ struct Pipeline {
             std::cout << "[MAIN] SAM stage: " << produce_ms << " ms between the rerank and the writer, " << aligned_rows
                       << " rows aligned, " << std::chrono::duration<double, std::milli>(clk::now() - t0).count()
                       << " ms for the block loop" << std::endl;
+        if (rc == DRM_OK && o.sam_sort)
+            write_sorted_sam();
         return rc;
     }
 
