@@ -184,40 +184,56 @@ def emb_table(w):
 
 # ------------------------------------------------------------------------------------- model
 def _sig(x):
-    return 1.0 / (1.0 + np.exp(-x))
+    with np.errstate(over="ignore"):   # exp(-x) = inf in float32 for x < -88.7: the gate is exactly 0
+        return 1.0 / (1.0 + np.exp(-x))
 
 
-def gru_direction(X, W, R, B, reverse, h0=0.0):
+def gru_direction(X, W, R, B, reverse, h0=0.0, dtype=np.float64, round_h=None, probe=None):
     """One direction of an OpenVINO GRUSequence with linear_before_reset (GRUCell-3 formulas):
     z = f(x Wz' + h Rz' + bz), r = f(x Wr' + h Rr' + br), n = g(x Wh' + Wbh + r * (h Rh' + Rbh)),
-    h = (1 - z) * n + z * h. X [n, L, in]; returns Y [n, L, 64] and the final h [n, 64]."""
+    h = (1 - z) * n + z * h. X [n, L, in]; returns Y [n, L, 64] and the final h [n, 64].
+    Test hooks (the defaults are the float64 oracle, bit for bit): dtype = the arithmetic's type;
+    round_h(h) = what of the state enters the recurrent product h R'; probe(z, r, n) is handed the three
+    pre-activations of every step."""
     n, L, _ = X.shape
     H = HIDDEN
-    h = np.full((n, H), h0, dtype=np.float64)
-    Y = np.empty((n, L, H), dtype=np.float64)
+    X, W, R, B = (np.asarray(a, dtype=dtype) for a in (X, W, R, B))
+    one = dtype(1.0)
+    h = np.full((n, H), h0, dtype=dtype)
+    Y = np.empty((n, L, H), dtype=dtype)
     GX = X @ W.T  # [n, L, 3H]
     for s in range(L):
         t = L - 1 - s if reverse else s
         gx = GX[:, t]
-        gh = h @ R.T
-        z = _sig(gx[:, :H] + gh[:, :H] + B[:H])
-        r = _sig(gx[:, H:2 * H] + gh[:, H:2 * H] + B[H:2 * H])
-        nn = np.tanh(gx[:, 2 * H:] + B[2 * H:3 * H] + r * (gh[:, 2 * H:] + B[3 * H:]))
-        h = (1.0 - z) * nn + z * h
+        gh = (h if round_h is None else round_h(h)) @ R.T
+        az = gx[:, :H] + gh[:, :H] + B[:H]
+        ar = gx[:, H:2 * H] + gh[:, H:2 * H] + B[H:2 * H]
+        z = _sig(az)
+        r = _sig(ar)
+        an = gx[:, 2 * H:] + B[2 * H:3 * H] + r * (gh[:, 2 * H:] + B[3 * H:])
+        if probe is not None:
+            probe(az, ar, an)
+        nn = np.tanh(an)
+        h = (one - z) * nn + z * h
         Y[:, t] = h
     return Y, h
 
 
-def encode_tokens(w, tokens):
-    """tokens [n, L] vocab ids (-1 -> the padding row, as the GPU does) -> embeddings [n, 128] f64."""
+def encode_tokens(w, tokens, dtype=np.float64, round_h=None, round_y1=None, probe=None):
+    """tokens [n, L] vocab ids (-1 -> the padding row, as the GPU does) -> embeddings [n, 128] of `dtype`.
+    Test hooks as in gru_direction; round_y1(Y1) = what of layer 1's output enters layer 2; probe(layer, z, r, n)."""
     tok = np.where(tokens < 0, 0, tokens)
     X = emb_table(w)(tok)
-    h0 = w.get("h0", 0.0)
-    yf, _ = gru_direction(X, w["W1"][0], w["R1"][0], w["B1"][0], False, h0)
-    yb, _ = gru_direction(X, w["W1"][1], w["R1"][1], w["B1"][1], True, h0)
+    h0 = dtype(w.get("h0", 0.0))
+    kw = [dict(h0=h0, dtype=dtype, round_h=round_h,
+               probe=None if probe is None else (lambda z, r, n, l=l: probe(l, z, r, n))) for l in (1, 2)]
+    yf, _ = gru_direction(X, w["W1"][0], w["R1"][0], w["B1"][0], False, **kw[0])
+    yb, _ = gru_direction(X, w["W1"][1], w["R1"][1], w["B1"][1], True, **kw[0])
     Y1 = np.concatenate([yf, yb], axis=2)
-    _, hf = gru_direction(Y1, w["W2"][0], w["R2"][0], w["B2"][0], False, h0)
-    _, hb = gru_direction(Y1, w["W2"][1], w["R2"][1], w["B2"][1], True, h0)
+    if round_y1 is not None:
+        Y1 = round_y1(Y1)
+    _, hf = gru_direction(Y1, w["W2"][0], w["R2"][0], w["B2"][0], False, **kw[1])
+    _, hb = gru_direction(Y1, w["W2"][1], w["R2"][1], w["B2"][1], True, **kw[1])
     return np.concatenate([hf, hb], axis=1)
 
 
