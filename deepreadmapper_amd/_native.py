@@ -49,7 +49,7 @@ EXPORTS = [
     "drm_sw_align_affine_clip", "drm_sw_align_affine_clip_device",
     "drm_sw_align_md", "drm_sw_align_md_device", "drm_sam_md",
     "drm_exact_search", "drm_exact_search_device", "drm_exact_search_l2", "drm_exact_search_l2_device",
-    "drm_flat_exact_search", "drm_exact_set_slice_rows", "drm_exact_query_tile",
+    "drm_flat_exact_search", "drm_exact_set_slice_rows", "drm_exact_query_tile", "drm_debug_exact_plan",
     "drm_pair_hits", "drm_pair_hits_device", "drm_sam_pair_fields",
     "drm_mate_rescue", "drm_mate_rescue_device", "drm_mate_rescue_region", "drm_mate_rescue_window",
     "drm_pair_rescue_choose",
@@ -273,6 +273,7 @@ def lib():
         "drm_flat_exact_search": (C.c_int, [vp, vp, i64, i32, i32, vp, vp, C.POINTER(C.c_double)]),
         "drm_exact_set_slice_rows": (C.c_int, [i64]),
         "drm_exact_query_tile": (C.c_int, []),
+        "drm_debug_exact_plan": (C.c_int, [i32, i64, i64, i32, C.POINTER(i64)]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name, None)

@@ -1299,6 +1299,12 @@ int drm_exact_set_slice_rows(int64_t rows)
 
 int drm_exact_query_tile(void) { return drm::exact_query_tile(); }
 
+// diagnostic: the plan run_scan would follow (exact_scan.hip: scan_plan), for the tests to see which path a case takes
+int drm_debug_exact_plan(int32_t kind, int64_t n, int64_t n_base, int32_t k, int64_t *out7)
+{
+    return guarded([&] { drm::exact_plan(kind, n, n_base, k, out7); });
+}
+
 // ------------------------------------------------------------------------------------ SW
 int drm_sw_scores(const uint8_t *s1, const int64_t *off1, const int32_t *len1, const uint8_t *s2,
                   const int64_t *off2, const int32_t *len2, int64_t npairs, int32_t *scores)

@@ -221,6 +221,9 @@ void launch_exact_l2(const float *d_base, int64_t n_base, int d, const float *d_
                      int64_t *d_I, const uint64_t *d_labels, hipStream_t stream, double *ms);
 int64_t exact_set_slice_rows(int64_t rows); // 0 = default; returns the value kept (rounded up to 64)
 int exact_query_tile();
+// the plan a scan of `kind` (0 PQ 8x8, 1 any other PQ shape, 2 fp32) would run with under the current slice rows:
+// out = {qt, step, cap, slice_rows, slices, chunk, chunks}. Launches nothing.
+void exact_plan(int kind, int64_t n, int64_t n_base, int k, int64_t out[7]);
 
 // ---------------------------------------------------------------------------------- SW rerank
 struct DeviceRefs {

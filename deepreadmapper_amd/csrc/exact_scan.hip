@@ -374,14 +374,32 @@ void check_launch(const char *what)
         throw Error(DRM_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
 }
 
-enum ScanKind { kScanPq8, kScanPqAny, kScanL2 };
+enum ScanKind { kScanPq8 = 0, kScanPqAny = 1, kScanL2 = 2 }; // the values of drm_debug_exact_plan's `kind`
 
-// the split of n_base rows into slices: one round of resident workgroups over the whole grid (wg_per_cu per CU: a
-// second round repeats every tile's LUT build and start-up sorts; 1,024 queries over 1M codes took 1.81 ms at 4
-// slices, one round, against 2.53 ms at 8 and 2.34 ms at 2, profiles/r08/slices_c3.txt), slices of 16 Ki rows or
-// more; or the rows drm_exact_set_slice_rows asked for, raised until at most kMaxSlices slices remain
-void choose_slices(int64_t n_base, int64_t tiles, int wg_per_cu, int64_t &slice_rows, int &slices)
+// The whole plan of one scan of n queries over n_base rows at k: every number run_scan launches with.
+//   qt, step         queries per tile and base rows per step of the kind's kernel
+//   cap              survivor buffer entries per (query, slice): the power of two >= k + step
+//   slice_rows, slices   the split of n_base rows: one round of resident workgroups over the whole grid (2 per CU
+//                    for PQ 8 x 8, 4 otherwise: a second round repeats every tile's LUT build and start-up sorts;
+//                    1,024 queries over 1M codes took 1.81 ms at 4 slices, one round, against 2.53 ms at 8 and
+//                    2.34 ms at 2, profiles/r08/slices_c3.txt), slices of 16 Ki rows or more; or the rows
+//                    drm_exact_set_slice_rows asked for, raised until at most kMaxSlices slices remain
+//   chunk, chunks    queries per launch, a multiple of qt whose partial lists fit kWorkspaceBytes, and the launches
+struct ScanPlan {
+    int qt, step, cap;
+    int64_t slice_rows;
+    int slices;
+    int64_t chunk, chunks;
+};
+
+ScanPlan scan_plan(ScanKind kind, int64_t n, int64_t n_base, int k)
 {
+    ScanPlan p{};
+    p.qt = kind == kScanPqAny ? 1 : kQT;
+    p.step = kind == kScanPq8 ? kScanThreads * kPqRowsPerThread : kScanThreads;
+    p.cap = pow2_at_least(k + p.step);
+    const int64_t tiles = (n + p.qt - 1) / p.qt;
+    const int wg_per_cu = kind == kScanPq8 ? 2 : 4;
     int64_t rows = g_slice_rows.load();
     if (rows <= 0) {
         int dev = 0, cus = 256;
@@ -393,28 +411,32 @@ void choose_slices(int64_t n_base, int64_t tiles, int wg_per_cu, int64_t &slice_
     }
     rows = std::max<int64_t>(rows, (n_base + kMaxSlices - 1) / kMaxSlices);
     rows = std::max<int64_t>(64, (rows + 63) / 64 * 64);
-    slice_rows = rows;
-    slices = (int)std::max<int64_t>(1, (n_base + rows - 1) / rows);
+    p.slice_rows = rows;
+    p.slices = (int)std::max<int64_t>(1, (n_base + rows - 1) / rows);
+    const int64_t per_query = (int64_t)p.slices * p.cap * 8;
+    int64_t chunk = std::max<int64_t>(1, kWorkspaceBytes / per_query) / p.qt * p.qt;
+    p.chunk = std::min(std::max<int64_t>(chunk, p.qt), tiles * p.qt);
+    p.chunks = (n + p.chunk - 1) / p.chunk;
+    return p;
 }
 
-// One scan: queries in chunks whose partial lists fit kWorkspaceBytes, each chunk a scan launch and a merge launch
-// on `stream`; synchronises the stream and frees the workspace before it returns. ms (may be null): device time of
-// the launches (events on `stream`).
+// One scan by its plan: queries in chunks whose partial lists fit kWorkspaceBytes, each chunk a scan launch and a
+// merge launch on `stream`; synchronises the stream and frees the workspace before it returns. ms (may be null):
+// device time of the launches (events on `stream`).
 void run_scan(ScanKind kind, ScanArgs a, float *d_D, int64_t *d_I, const uint64_t *d_labels, hipStream_t stream,
               double *ms)
 {
-    const int qt = kind == kScanPqAny ? 1 : kQT;
-    const int step = kind == kScanPq8 ? kScanThreads * kPqRowsPerThread : kScanThreads;
     const int64_t n = a.sa.n;
     const int d = a.sa.d;
     const float *x = a.sa.x;
-    a.cap = pow2_at_least(a.k + step);
-    choose_slices(a.n_base, (n + qt - 1) / qt, kind == kScanPq8 ? 2 : 4, a.slice_rows, a.slices);
-    const int64_t per_query = (int64_t)a.slices * a.cap * 8;
-    int64_t chunk = std::max<int64_t>(1, kWorkspaceBytes / per_query) / qt * qt;
-    chunk = std::min(std::max<int64_t>(chunk, qt), (n + qt - 1) / qt * qt);
+    const ScanPlan p = scan_plan(kind, n, a.n_base, a.k);
+    const int qt = p.qt;
+    const int64_t chunk = p.chunk;
+    a.cap = p.cap;
+    a.slice_rows = p.slice_rows;
+    a.slices = p.slices;
     uint64_t *ws = nullptr;
-    DRM_HIP_CHECK(hipMalloc(&ws, (size_t)(chunk * per_query)));
+    DRM_HIP_CHECK(hipMalloc(&ws, (size_t)(chunk * p.slices * p.cap * 8)));
     hipEvent_t e0 = nullptr, e1 = nullptr;
     try {
         if (ms) {
@@ -423,8 +445,8 @@ void run_scan(ScanKind kind, ScanArgs a, float *d_D, int64_t *d_I, const uint64_
             DRM_HIP_CHECK(hipEventRecord(e0, stream));
         }
         a.ws = ws;
-        for (int64_t q0 = 0; q0 < n; q0 += chunk) {
-            const int64_t nq = std::min(chunk, n - q0);
+        for (int64_t c = 0; c < p.chunks; ++c) {
+            const int64_t q0 = c * chunk, nq = std::min(chunk, n - q0);
             a.sa.x = x + q0 * d;
             a.sa.n = nq;
             const dim3 grid((unsigned)((nq + qt - 1) / qt), (unsigned)a.slices);
@@ -479,6 +501,21 @@ void check_nk(int64_t n, int k)
 } // namespace
 
 int exact_query_tile() { return kQT; }
+
+void exact_plan(int kind, int64_t n, int64_t n_base, int k, int64_t out[7])
+{
+    if (kind < kScanPq8 || kind > kScanL2 || n_base < 0 || n_base >= (int64_t)1 << 31 || !out)
+        throw Error(DRM_ERR_ARG, "drm_debug_exact_plan: kind in [0, 2], 0 <= n_base < 2^31, an output");
+    check_nk(n, k);
+    const ScanPlan p = scan_plan((ScanKind)kind, n, n_base, k);
+    out[0] = p.qt;
+    out[1] = p.step;
+    out[2] = p.cap;
+    out[3] = p.slice_rows;
+    out[4] = p.slices;
+    out[5] = p.chunk;
+    out[6] = p.chunks;
+}
 
 int64_t exact_set_slice_rows(int64_t rows)
 {

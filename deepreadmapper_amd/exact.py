@@ -19,6 +19,19 @@ def set_slice_rows(rows):
     check(lib().drm_exact_set_slice_rows(int(rows)))
 
 
+SCAN_KINDS = {"pq8": 0, "pq": 1, "l2": 2}  # drm_debug_exact_plan's `kind`
+PLAN_FIELDS = ("qt", "step", "cap", "slice_rows", "slices", "chunk", "chunks")
+
+
+def scan_plan(kind, n, n_base, k):
+    """drm_debug_exact_plan: the plan a scan of `kind` ("pq8": PQ 8x8 with aligned queries, "pq": any other PQ scan,
+    "l2": fp32) of n queries over n_base rows at k would run with under the current slice rows, as a dict of
+    PLAN_FIELDS. From the function the scans use; launches nothing."""
+    out = (C.c_int64 * 7)()
+    check(lib().drm_debug_exact_plan(SCAN_KINDS[kind], int(n), int(n_base), int(k), out))
+    return dict(zip(PLAN_FIELDS, (int(v) for v in out)))
+
+
 def _queries(x):
     x = np.ascontiguousarray(x, dtype=np.float32)
     if x.ndim != 2:

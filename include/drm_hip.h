@@ -237,6 +237,12 @@ int drm_flat_exact_search(drm_flat_index *index, const float *x, int64_t n, int3
 int drm_exact_set_slice_rows(int64_t rows);
 /* Queries per workgroup tile of the PQ 8 x 8 scan (for the tests' batch-edge cases). */
 int drm_exact_query_tile(void);
+/* Diagnostic: the plan a scan of n queries over n_base rows at k would run with under the current slice rows, from
+ * the function the scans themselves use. kind: 0 = PQ 8 x 8 with 16-byte aligned queries, 1 = any other PQ scan,
+ * 2 = fp32. out7 = {queries per tile, base rows per step, cap (survivor buffer entries per (query, slice)), rows per
+ * slice, slices, queries per launch, launches}. Launches nothing. Arguments outside the scans' limits -> the scans'
+ * errors. For the tests. */
+int drm_debug_exact_plan(int32_t kind, int64_t n, int64_t n_base, int32_t k, int64_t *out7);
 
 /* ---------------------------------------------------------------- Smith-Waterman rerank */
 /* Batched calc_sw_score(seq1, seq2) (includes/utils/metrics.hpp:22, src/utils/metrics.cpp:10-45):
