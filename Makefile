@@ -16,8 +16,8 @@ HOSTFLAGS := $(COMMON) -fopenmp -ffp-contract=off -D__HIP_PLATFORM_AMD__ -I$(ROC
 
 LIB := $(PKG)/libdrm_hip.so
 HIP_OBJS := $(BUILD)/hnsw_search.o $(BUILD)/hnsw_pq_fast.o $(BUILD)/builder_gpu.o $(BUILD)/embed_gpu.o $(BUILD)/hnsw_search_lds.o $(BUILD)/hnsw_flat_search.o $(BUILD)/sw_rerank.o $(BUILD)/l2_rerank.o \
-            $(BUILD)/encoder_gru.o $(BUILD)/sw_align.o $(BUILD)/sw_align_affine.o $(BUILD)/sw_md.o $(BUILD)/pair_hits.o $(BUILD)/mate_rescue.o $(BUILD)/mapq.o $(BUILD)/hit_loci.o $(BUILD)/tlen_scan.o $(BUILD)/contig_hits.o $(BUILD)/dup_set.o $(BUILD)/sort_order.o $(BUILD)/exact_scan.o $(BUILD)/capi.o $(BUILD)/exec.o
-HOST_OBJS := $(BUILD)/faiss_io.o $(BUILD)/formats.o $(BUILD)/sam.o $(BUILD)/read_rules.o $(BUILD)/builder.o $(BUILD)/embed.o $(BUILD)/hnswlib_io.o \
+            $(BUILD)/encoder_gru.o $(BUILD)/sw_align.o $(BUILD)/sw_align_affine.o $(BUILD)/sw_md.o $(BUILD)/pair_hits.o $(BUILD)/mate_rescue.o $(BUILD)/mapq.o $(BUILD)/hit_loci.o $(BUILD)/tlen_scan.o $(BUILD)/contig_hits.o $(BUILD)/dup_set.o $(BUILD)/sort_order.o $(BUILD)/bgzf.o $(BUILD)/exact_scan.o $(BUILD)/capi.o $(BUILD)/exec.o
+HOST_OBJS := $(BUILD)/faiss_io.o $(BUILD)/formats.o $(BUILD)/sam.o $(BUILD)/bam.o $(BUILD)/read_rules.o $(BUILD)/builder.o $(BUILD)/embed.o $(BUILD)/hnswlib_io.o \
              $(BUILD)/builder_flat.o $(BUILD)/encoder.o
 HDRS := include/drm_hip.h $(SRC)/drm_internal.h $(SRC)/drm_device.h $(SRC)/pq_common.h $(SRC)/locus_scan.h $(SRC)/sw_wave.h
 

@@ -25,6 +25,8 @@ from .contigs import ContigTable, contig_hits, contig_hits_device, fasta_contigs
 from .dups import DupSet, dup_end_word, dup_slot, sam_end5  # noqa: F401  (duplicate marking: a first-seen set)
 from .sorting import (sam_sort_key, sort_order, sort_order_device, sort_order_workspace, sort_scan_tiles,  # noqa: F401
                       sort_tile)  # (coordinate order: a stable radix sort)
+from .bam import (bam_header, bam_record, bgzf_block, bgzf_bound, bgzf_compress, bgzf_compress_device,  # noqa: F401
+                  bgzf_eof, bgzf_workspace)  # (BAM output: BGZF on the device, the record encoder)
 
 __version__ = "0.4.0"
 from .executor import Comm, MultiIndex, search_rerank  # noqa: F401  (batch executor, multi-GPU, RCCL gather)

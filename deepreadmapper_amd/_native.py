@@ -63,6 +63,8 @@ EXPORTS = [
     "drm_dupset_mark", "drm_dupset_mark_device",
     "drm_sam_sort_key", "drm_sort_tile", "drm_sort_scan_tiles", "drm_sort_order", "drm_sort_order_workspace",
     "drm_sort_order_device",
+    "drm_bgzf_block", "drm_bgzf_bound", "drm_bgzf_eof", "drm_bgzf_compress", "drm_bgzf_workspace",
+    "drm_bgzf_compress_device", "drm_bam_header", "drm_bam_record",
 ]
 
 
@@ -266,6 +268,14 @@ def lib():
         "drm_sort_order": (C.c_int, [vp, i64, C.c_int, vp]),
         "drm_sort_order_workspace": (C.c_int, [i64, C.POINTER(sz)]),
         "drm_sort_order_device": (C.c_int, [vp, i64, vp, vp, sz, vp]),
+        "drm_bgzf_block": (C.c_int, []),
+        "drm_bgzf_bound": (C.c_int, [i64, C.POINTER(sz)]),
+        "drm_bgzf_eof": (C.c_int, [vp]),
+        "drm_bgzf_compress": (C.c_int, [vp, i64, C.c_int, vp, sz, C.POINTER(sz)]),
+        "drm_bgzf_workspace": (C.c_int, [i64, C.POINTER(sz)]),
+        "drm_bgzf_compress_device": (C.c_int, [vp, i64, vp, vp, vp, sz, vp]),
+        "drm_bam_header": (C.c_int, [C.c_char_p, sz, vp, sz, C.POINTER(sz)]),
+        "drm_bam_record": (C.c_int, [C.c_char_p, sz, vp, i32, vp, sz, C.POINTER(sz)]),
         "drm_exact_search": (C.c_int, [vp, vp, i64, i32, i32, vp, vp, C.POINTER(C.c_double)]),
         "drm_exact_search_device": (C.c_int, [vp, vp, i64, i32, vp, vp, vp]),
         "drm_exact_search_l2": (C.c_int, [vp, i64, i32, vp, i64, i32, vp, vp, C.POINTER(C.c_double)]),

@@ -2793,6 +2793,157 @@ int drm_sort_order(const uint64_t *keys, int64_t n, int device, uint32_t *order)
     });
 }
 
+// ---------------------------------------------------------------------- BGZF compression (bgzf.hip)
+// every check of a compress call, before anything is touched; false when there is nothing to do
+static bool bgzf_checked(const void *data, int64_t n, const void *out)
+{
+    if (n < 0)
+        throw Error(DRM_ERR_ARG, "n must be >= 0");
+    if (n == 0)
+        return false;
+    if (!data || !out)
+        throw Error(DRM_ERR_ARG, "null argument");
+    return true;
+}
+
+static size_t bgzf_bound(int64_t n) { return (size_t)n + 31 * (size_t)drm::bgzf_blocks(n); }
+// the launcher's workspace plus what aligning the caller's pointer to 256 bytes may cost
+static size_t bgzf_work_bytes(int64_t n) { return drm::bgzf_workspace_bytes(n) + 256; }
+
+int drm_bgzf_workspace(int64_t n, size_t *bytes)
+{
+    return guarded([&] {
+        if (!bytes)
+            throw Error(DRM_ERR_ARG, "null argument");
+        if (n < 0)
+            throw Error(DRM_ERR_ARG, "n must be >= 0");
+        *bytes = n == 0 ? 0 : bgzf_work_bytes(n);
+    });
+}
+
+int drm_bgzf_compress_device(const uint8_t *d_data, int64_t n, uint8_t *d_out, uint32_t *d_sizes, void *d_work,
+                             size_t work_bytes, void *stream)
+{
+    return guarded([&] {
+        if (!bgzf_checked(d_data, n, d_out))
+            return;
+        if (!d_sizes)
+            throw Error(DRM_ERR_ARG, "null argument");
+        if (!d_work || work_bytes < bgzf_work_bytes(n))
+            throw Error(DRM_ERR_ARG, "the workspace holds " + std::to_string(work_bytes) + " bytes, " +
+                                         std::to_string(bgzf_work_bytes(n)) + " are needed (drm_bgzf_workspace)");
+        void *aligned = reinterpret_cast<void *>(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
+        drm::launch_bgzf(d_data, n, d_out, d_sizes, aligned, (hipStream_t)stream);
+    });
+}
+
+// What the host form keeps between calls: a stream of its own (the SAM writer thread compresses while the main thread
+// drives the executor's streams), pinned staging on both sides and the device buffers of one round. One per process,
+// rebuilt when another device is asked for; calls are serialised by its mutex. It lives until the process ends.
+namespace {
+struct BgzfContext {
+    std::mutex mu;
+    int device = -1;
+    hipStream_t stream = nullptr;
+    size_t cap = 0; // input bytes of one round that the buffers hold
+    uint8_t *h_in = nullptr, *h_out = nullptr, *d_in = nullptr, *d_out = nullptr, *d_work = nullptr;
+    uint32_t *d_sizes = nullptr;
+    uint64_t *h_total = nullptr;
+
+    void release()
+    {
+        if (stream)
+            (void)hipStreamDestroy(stream);
+        (void)hipHostFree(h_in);
+        (void)hipHostFree(h_out);
+        (void)hipHostFree(h_total);
+        (void)hipFree(d_in);
+        (void)hipFree(d_out);
+        (void)hipFree(d_work);
+        (void)hipFree(d_sizes);
+        device = -1;
+        stream = nullptr;
+        cap = 0;
+        h_in = h_out = d_in = d_out = d_work = nullptr;
+        d_sizes = nullptr;
+        h_total = nullptr;
+    }
+    void reserve(int dev, size_t bytes)
+    {
+        if (dev == device && bytes <= cap)
+            return;
+        release();
+        DRM_HIP_CHECK(hipSetDevice(dev));
+        device = dev;
+        DRM_HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        const size_t blocks = (size_t)drm::bgzf_blocks((int64_t)bytes);
+        DRM_HIP_CHECK(hipHostMalloc((void **)&h_in, bytes, hipHostMallocDefault));
+        DRM_HIP_CHECK(hipHostMalloc((void **)&h_out, bgzf_bound((int64_t)bytes), hipHostMallocDefault));
+        DRM_HIP_CHECK(hipHostMalloc((void **)&h_total, sizeof(uint64_t), hipHostMallocDefault));
+        DRM_HIP_CHECK(hipMalloc((void **)&d_in, bytes));
+        DRM_HIP_CHECK(hipMalloc((void **)&d_out, bgzf_bound((int64_t)bytes)));
+        DRM_HIP_CHECK(hipMalloc((void **)&d_work, drm::bgzf_workspace_bytes((int64_t)bytes)));
+        DRM_HIP_CHECK(hipMalloc((void **)&d_sizes, sizeof(uint32_t) * blocks));
+        cap = bytes;
+    }
+};
+BgzfContext g_bgzf;
+
+// BGZF blocks per round of the host form: 256 (16 MiB of input), or DRM_BGZF_ROUND, read at every call
+int64_t bgzf_round_blocks()
+{
+    const char *e = std::getenv("DRM_BGZF_ROUND");
+    if (!e)
+        return 256;
+    char *end = nullptr;
+    const long long v = std::strtoll(e, &end, 10);
+    if (end == e || *end != '\0' || v < 1 || v > (1 << 20))
+        throw Error(DRM_ERR_ARG, std::string("DRM_BGZF_ROUND must be an integer in [1, 2^20]: \"") + e + "\"");
+    return v;
+}
+} // namespace
+
+int drm_bgzf_compress(const uint8_t *data, int64_t n, int device, uint8_t *out, size_t cap, size_t *bytes)
+{
+    return guarded([&] {
+        if (!bytes)
+            throw Error(DRM_ERR_ARG, "null argument");
+        *bytes = 0;
+        if (!bgzf_checked(data, n, out))
+            return;
+        if (device < 0)
+            throw Error(DRM_ERR_ARG, "negative device");
+        if (cap < bgzf_bound(n))
+            throw Error(DRM_ERR_ARG, "cap " + std::to_string(cap) + " is below drm_bgzf_bound's " +
+                                         std::to_string(bgzf_bound(n)));
+        const int64_t round = bgzf_round_blocks() * drm::kBgzfBlock; // checked before anything is touched
+        std::lock_guard<std::mutex> lock(g_bgzf.mu);
+        BgzfContext &c = g_bgzf;
+        c.reserve(device, (size_t)std::min(n, round));
+        DRM_HIP_CHECK(hipSetDevice(device));
+        size_t done = 0;
+        // a round ends on a block boundary, and a member depends on its block's bytes alone: the stream is the same for
+        // every round size
+        for (int64_t from = 0; from < n; from += round) {
+            const int64_t m = std::min(round, n - from);
+            std::memcpy(c.h_in, data + from, (size_t)m);
+            DRM_HIP_CHECK(hipMemcpyAsync(c.d_in, c.h_in, (size_t)m, hipMemcpyHostToDevice, c.stream));
+            drm::launch_bgzf(c.d_in, m, c.d_out, c.d_sizes, c.d_work, c.stream);
+            DRM_HIP_CHECK(hipMemcpyAsync(c.h_total, drm::bgzf_total(c.d_work, m), sizeof(uint64_t), hipMemcpyDeviceToHost,
+                                         c.stream));
+            DRM_HIP_CHECK(hipStreamSynchronize(c.stream));
+            const size_t got = (size_t)*c.h_total;
+            if (got > bgzf_bound(m))
+                throw Error(DRM_ERR_INTERNAL, "the members of a round hold " + std::to_string(got) + " bytes, above the bound");
+            DRM_HIP_CHECK(hipMemcpyAsync(c.h_out, c.d_out, got, hipMemcpyDeviceToHost, c.stream));
+            DRM_HIP_CHECK(hipStreamSynchronize(c.stream));
+            std::memcpy(out + done, c.h_out, got);
+            done += got;
+        }
+        *bytes = done;
+    });
+}
+
 // ------------------------------------------------------------------------------- L2 rerank
 static drm::L2Args make_l2_args(drm_refs *refs, bool dynamic, const int64_t *nb, int64_t nq, int32_t kk,
                                 const float *qe, int32_t d, int64_t stride, int32_t k, int32_t k_clusters, float *td,

@@ -500,6 +500,28 @@ size_t sort_workspace_bytes(int64_t n);
 // d_work holds sort_workspace_bytes(n) bytes, 256-byte aligned
 void launch_sort_order(const uint64_t *d_keys, int64_t n, uint32_t *d_order, void *d_work, hipStream_t stream);
 
+// BGZF compression (bgzf.hip; drm_bgzf_compress): input byte i belongs to block i / kBgzfBlock; one
+// workgroup turns one block into one complete gzip member in the block's kBgzfSlot-byte slot, a scan turns the members'
+// sizes into offsets, and a copy packs the members back to back. A grid of at most kBgzfGrid workgroups walks the blocks;
+// each workgroup keeps the tokens of the block it is working on in its own kBgzfBlock words of scratch. Runs on the
+// current device; the entry points check the pointers and the workspace before it is called.
+constexpr int kBgzfSlot = 65536, kBgzfGrid = 512; // kBgzfBlock: drm_internal.h
+struct BgzfArgs {
+    const uint8_t *data; // [n], never written
+    int64_t n, blocks;
+    uint8_t *slots;    // [blocks][kBgzfSlot]: member b, 4-byte aligned
+    uint32_t *tokens;  // [min(blocks, kBgzfGrid)][kBgzfBlock]: a workgroup's parse between its count and its emit pass
+    uint32_t *sizes;   // [blocks]: member b's bytes (the caller's array)
+    uint64_t *offsets; // [blocks + 1]: member b's first byte in the packed stream; the last one is the stream's length
+    uint8_t *out;      // the packed stream (the caller's array)
+};
+int64_t bgzf_blocks(int64_t n);
+size_t bgzf_workspace_bytes(int64_t n);
+// d_work holds bgzf_workspace_bytes(n) bytes, 256-byte aligned
+void launch_bgzf(const uint8_t *d_data, int64_t n, uint8_t *d_out, uint32_t *d_sizes, void *d_work, hipStream_t stream);
+// where launch_bgzf leaves the packed stream's length (a uint64_t) inside d_work
+const uint64_t *bgzf_total(const void *d_work, int64_t n);
+
 // L2 rerank (post_process_l2_static -> batch_reranker, src/utils/post_processor.cpp:1023-1162,
 // src/utils/reranker.cpp:98-195): distances from the window embedding table, libstdc++ partial_sort
 struct L2Args {

@@ -4,6 +4,7 @@
 #include <new>
 #include <stdexcept>
 #include <string>
+#include <string_view>
 #include <unordered_map>
 #include <variant>
 #include <vector>
@@ -223,6 +224,10 @@ struct SamBlock {
     // DRM_SAM_SORT=coordinate (null = the lines go to the file): the writers touch no file; every line they build is
     // appended to the spool instead, in the order in which it would have been written
     struct SamSpool *spool = nullptr;
+    // DRM_SAM_FORMAT=bam (null = SAM text): every line is encoded as a BAM alignment record (bam_encode_line). Without
+    // a spool the records go to this sink, which the first block (header) opens on `path`; with a spool they are what
+    // the spool holds in place of text
+    class BamSink *bam = nullptr;
 };
 // The lines of a run held back until their order is known: line i is text[offsets[i] .. offsets[i + 1]) (the last one
 // to the end), newline included, and keys[i] its drm_sam_sort_key. All of it lives in host memory, a few hundred bytes
@@ -234,6 +239,68 @@ struct SamSpool {
 // The sorted file: @HD VN:1.0 SO:coordinate, b's @SQ lines (path, ref_name, ref_len and ctg->table are read), then line
 // order[i] of the spool for i = 0 .. The file is written beside b.path and renamed over it when complete.
 void write_sam_sorted(const SamBlock &b, const SamSpool &spool, const uint32_t *order);
+
+// The eleven columns of one line and its tags. `reversed` is the orientation of columns 10 and 11: SEQ
+// reverse-complemented and QUAL reversed, or both as read. An empty read or quality line prints "*".
+struct SamLine {
+    std::string_view qname;
+    int flag = 0;
+    std::string_view rname = "*";
+    int64_t pos = 0;
+    int mapq = 0;
+    std::string_view cigar = "*", rnext = "*";
+    int64_t pnext = 0, tlen = 0;
+    std::string_view read, qual;
+    bool reversed = false;
+    std::string tags; // "\tAS:i:..\tNM:i:..[\tMD:Z:..][\tXA:Z:..]" of a mapped row, else empty
+};
+// The index of every reference name among the @SQ lines
+using SamRefIds = std::unordered_map<std::string_view, int64_t>;
+// Appends the BAM alignment record of one line (SAMv1 sec. 4.2, block_size first; include/drm_hip.h, drm_bam_record, has
+// the rules and the errors). The one encoder: drm_bam_record parses its text into a SamLine and calls this, and the
+// writers call it with the line they built.
+void bam_encode_line(const SamLine &l, const SamRefIds &refs, std::string &out);
+// "BAM\1", l_text, the text, n_ref and per @SQ line of the text l_name, name, NUL, l_ref (drm_bam_header)
+void bam_encode_header(std::string_view text, std::string &out);
+
+// the input bytes of one BGZF block (htslib's BGZF_BLOCK_SIZE); drm_bgzf_block
+constexpr int kBgzfBlock = 65280;
+// DRM_SAM_FORMAT=bam: where the writers of sam.cpp send a run's BAM bytes. They know this interface alone, so that
+// sam.cpp stands without the encoder and the compressor behind it: encode() appends one line's record, begin() opens the
+// file and takes the header, records are appended to pending() and flush() is called behind each, finish() ends the file.
+class BamSink {
+public:
+    virtual ~BamSink() = default;
+    virtual void encode(const SamLine &l, const SamRefIds &refs, std::string &to) = 0;
+    virtual void begin(const std::string &path, std::string_view header_text) = 0;
+    virtual std::string &pending() = 0;
+    virtual void flush(bool all = false) = 0;
+    virtual void finish() = 0;
+};
+// The sink of bin/pipeline (bam.cpp): encode() is bam_encode_line; the bytes are compressed by drm_bgzf_compress on
+// `device` in whole multiples of the 65,280-byte BGZF block whenever about 4 MiB have come together, the tail is carried
+// on, and finish() compresses what is left and adds the empty EOF member. The file is therefore a function of the byte
+// stream alone, whatever blocks the stream arrived in.
+class BamFile : public BamSink {
+public:
+    int device = 0;
+    uint64_t bytes_in = 0, bytes_out = 0; // DRM_SAM_STATS: what went into the compression and what came out
+    double compress_ms = 0;              // and the time inside drm_bgzf_compress
+    void encode(const SamLine &l, const SamRefIds &refs, std::string &to) override;
+    void begin(const std::string &path, std::string_view header_text) override;
+    std::string &pending() override { return buf; }
+    void flush(bool all = false) override;
+    void finish() override; // throws Error(DRM_ERR_IO) when the file did not take it all
+    ~BamFile() override;
+
+private:
+    std::string buf, file_path;
+    std::vector<uint8_t> packed;
+    void *file = nullptr; // a FILE *
+};
+// The sorted BAM file, write_sam_sorted's twin: the header under SO:coordinate, then record order[i] of the spool (whose
+// text holds encoded records) for i = 0 .., through b.bam onto b.path + ".part", renamed over b.path when complete.
+void write_bam_sorted(const SamBlock &b, const SamSpool &spool, const uint32_t *order);
 // The SAM lines of queries [q0, q0 + nq): query i has the rows i * k + j, j < counts[i]; row 0 is the primary, later
 // rows secondaries (flag 256). Without alignments a row prints the reference's pseudo fields
 //   QNAME FLAG ref <window's start + 1> 60 <read length>M * 0 0 SEQ QUAL       (SEQ and QUAL as read, also under flag 16)

@@ -4,10 +4,13 @@
 // DRM_SAM_SORT=coordinate: SamOut appends the lines to a SamSpool with their sort keys (drm_sam_sort_key) instead of
 // writing them, and write_sam_sorted writes the spool in a given order under @HD SO:coordinate. The spool holds the whole
 // run in host memory; an external merge for runs that do not fit is not implemented.
+// DRM_SAM_FORMAT=bam: SamOut sends every line through SamBlock::bam (drm_internal.h, BamSink; bam.cpp has the encoder
+// and the file), to the sink or to the spool, and write_bam_sorted is write_sam_sorted's twin over encoded records.
 #include <array>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
+#include <sstream>
 #include <string_view>
 #include <unordered_map>
 
@@ -234,21 +237,6 @@ const FastaContig *contig_of(const SamContigs *ctg, size_t row)
     return ctg ? &(*ctg->table)[(size_t)ctg->row_contig[row]] : nullptr;
 }
 
-// The eleven columns of one line and its tags. `reversed` is the orientation of columns 10 and 11: SEQ
-// reverse-complemented and QUAL reversed, or both as read. An empty read or quality line prints "*".
-struct SamLine {
-    std::string_view qname;
-    int flag = 0;
-    std::string_view rname = "*";
-    int64_t pos = 0;
-    int mapq = 0;
-    std::string_view cigar = "*", rnext = "*";
-    int64_t pnext = 0, tlen = 0;
-    std::string_view read, qual;
-    bool reversed = false;
-    std::string tags; // "\tAS:i:..\tNM:i:..[\tMD:Z:..][\tXA:Z:..]" of a mapped row, else empty
-};
-
 void append_line(std::string &buf, const SamLine &l)
 {
     auto column = [&](std::string_view s) { buf.append(s).push_back('\t'); };
@@ -327,6 +315,14 @@ void write_header(std::ostream &out, const SamBlock &b, const char *order)
             out << "@SQ\tSN:" << c.name << "\tLN:" << c.len << "\n";
 }
 
+// exactly the text write_header writes: what the BAM header holds
+std::string header_text(const SamBlock &b, const char *order)
+{
+    std::ostringstream text;
+    write_header(text, b, order);
+    return text.str();
+}
+
 uint64_t sam_sort_key(int64_t tid, int64_t pos, bool reverse)
 {
     if (tid == -1)
@@ -342,20 +338,36 @@ uint64_t sam_sort_key(int64_t tid, int64_t pos, bool reverse)
 // it passes 4 MiB at the end of a record, and after the last one. A block that throws leaves the rest unwritten.
 // With a spool (DRM_SAM_SORT=coordinate) no file is touched: every line goes to the spool's text, with its offset and
 // its sort key (drm_sam_sort_key of the index of its RNAME among the @SQ lines, its POS and its flag's bit 16).
+// With a BAM sink (DRM_SAM_FORMAT=bam) a line is its BAM record (BamSink::encode) wherever its text would have gone: in
+// the spool, or in the sink, which the block with the header opens and which compresses and writes on its own schedule.
 class SamOut {
     std::ofstream out;
     std::string buf;
     SamSpool *spool;
-    std::unordered_map<std::string_view, int64_t> tid; // spool only: RNAME -> its first @SQ line
-public:
-    explicit SamOut(const SamBlock &b) : spool(b.spool)
+    BamSink *bam;
+    SamRefIds tid; // spool or BAM: RNAME -> its first @SQ line
+    void put(std::string &to, const SamLine &l)
     {
-        if (spool) {
+        if (bam)
+            bam->encode(l, tid, to);
+        else
+            append_line(to, l);
+    }
+public:
+    explicit SamOut(const SamBlock &b) : spool(b.spool), bam(b.bam)
+    {
+        if (spool || bam) {
             if (!b.ctg)
                 tid.emplace(b.ref_name, 0);
             else
                 for (size_t i = 0; i < b.ctg->table->size(); ++i)
                     tid.emplace((*b.ctg->table)[i].name, (int64_t)i);
+        }
+        if (spool)
+            return;
+        if (bam) {
+            if (b.header)
+                bam->begin(b.path, header_text(b, "unsorted"));
             return;
         }
         out.open(b.path, b.header ? std::ios::out : std::ios::app);
@@ -367,7 +379,7 @@ public:
     void line(const SamLine &l)
     {
         if (!spool) {
-            append_line(buf, l);
+            put(bam ? bam->pending() : buf, l);
             return;
         }
         int64_t t = -1;
@@ -379,11 +391,17 @@ public:
         }
         spool->keys.push_back(sam_sort_key(t, l.pos, (l.flag & 16) != 0));
         spool->offsets.push_back(spool->text.size());
-        append_line(spool->text, l);
+        put(spool->text, l);
     }
     void end_record(bool last = false)
     {
-        if (spool || (!last && buf.size() <= (1u << 22)))
+        if (spool)
+            return;
+        if (bam) { // the tail is carried into the next block; the run's last bytes are BamSink::finish's
+            bam->flush();
+            return;
+        }
+        if (!last && buf.size() <= (1u << 22))
             return;
         out << buf;
         buf.clear();
@@ -549,6 +567,33 @@ void drm::write_sam_sorted(const SamBlock &b, const SamSpool &spool, const uint3
         out.close();
         if (!out)
             throw Error(DRM_ERR_IO, "Failed to write SAM file: " + part);
+        if (std::rename(part.c_str(), b.path.c_str()) != 0)
+            throw Error(DRM_ERR_IO, "Failed to rename " + part + " to " + b.path);
+    } catch (...) {
+        std::remove(part.c_str());
+        throw;
+    }
+}
+
+void drm::write_bam_sorted(const SamBlock &b, const SamSpool &spool, const uint32_t *order)
+{
+    const size_t n = spool.keys.size();
+    if (spool.offsets.size() != n || (n > 0 && !order) || !b.bam)
+        throw Error(DRM_ERR_ARG, "the spool's records, keys and order do not match, or there is no BAM sink");
+    // written beside the file and renamed when complete, as write_sam_sorted does
+    const std::string part = b.path + ".part";
+    try {
+        b.bam->begin(part, header_text(b, "coordinate"));
+        for (size_t i = 0; i < n; ++i) {
+            const size_t l = order[i];
+            if (l >= n)
+                throw Error(DRM_ERR_INTERNAL, "order[" + std::to_string(i) + "] = " + std::to_string(l) + " of " +
+                                                  std::to_string(n) + " records");
+            const size_t from = spool.offsets[l], to = l + 1 < n ? spool.offsets[l + 1] : spool.text.size();
+            b.bam->pending().append(spool.text, from, to - from);
+            b.bam->flush();
+        }
+        b.bam->finish();
         if (std::rename(part.c_str(), b.path.c_str()) != 0)
             throw Error(DRM_ERR_IO, "Failed to rename " + part + " to " + b.path);
     } catch (...) {

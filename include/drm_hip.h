@@ -973,6 +973,66 @@ int drm_sort_order_workspace(int64_t n, size_t *bytes);
 int drm_sort_order_device(const uint64_t *d_keys, int64_t n, uint32_t *d_order, void *d_work, size_t work_bytes,
                           void *stream);
 
+/* ---------------------------------------------------------------- BAM output (BGZF on the GPU, the record encoder)
+ * bin/pipeline's DRM_SAM_FORMAT=bam writes results.bam instead of results.sam: the BAM header, one alignment record per
+ * line the SAM would have held, in the same order, compressed as BGZF, closed by the empty EOF member. The reference has
+ * no BAM output, so this text, SAMv1 sec. 4 and RFC 1951 / 1952 are the definition.
+ *
+ * BGZF. Input byte i belongs to block i / 65280 (drm_bgzf_block, htslib's BGZF_BLOCK_SIZE). Every block becomes one gzip
+ * member, and the members follow each other without gaps:
+ *   1f 8b 08 04 | 00 00 00 00 | 00 ff | 06 00 | 42 43 02 00 | BSIZE-1 (u16 LE)
+ *   raw DEFLATE payload: one block with BFINAL = 1
+ *   CRC-32 of the block's bytes (u32 LE) | ISIZE = the block's length (u32 LE)
+ * BSIZE is the member's length. The payload is fixed Huffman (BTYPE = 01: LZ77 matches of length 4 .. 258 at distance
+ * 1 .. 32768 that neither start before the block's first byte nor end after its last, the codes of RFC 1951 sec. 3.2.6,
+ * end of block, zero bits up to a byte) unless that would be longer than len + 5 bytes; then it is stored (BTYPE = 00:
+ * 01 | LEN | ~LEN | the bytes). A member is therefore at most len + 31 bytes, drm_bgzf_bound(n) = n + 31 * ceil(n /
+ * 65280) bounds a stream, and every member can be inflated on its own. No dynamic Huffman tables.
+ * A member is a function of its block's bytes alone: the same in every run, wherever the block sits in a call, whatever
+ * else the device does (bgzf.hip: the match candidates come from LDS atomicMax / atomicMin updates, which do not depend
+ * on their order, and the greedy parse is resolved by pointer jumping). So compress(A || B) = compress(A) || compress(B)
+ * whenever |A| is a multiple of 65280.
+ * drm_bgzf_eof: the 28 bytes of the empty member that ends a BGZF file,
+ *   1f 8b 08 04 00 00 00 00 00 ff 06 00 42 43 02 00 1b 00 03 00 00 00 00 00 00 00 00 00.
+ * drm_bgzf_compress: host memory in and out; runs on `device`, on a stream of its own that it alone waits for (a thread
+ * may call it while another drives other streams), with stream-ordered copies through pinned staging, in rounds of 256
+ * blocks (the environment variable DRM_BGZF_ROUND, read at every call, sets another number in [1, 2^20], anything else
+ * being DRM_ERR_ARG; the stream does not depend on it). *bytes gets the stream's length. n == 0 is DRM_OK with 0 bytes before any device call; n < 0, a null pointer with n > 0, a negative
+ * device or cap < drm_bgzf_bound(n) is DRM_ERR_ARG with nothing launched. Calls are serialised inside.
+ * drm_bgzf_compress_device: device memory on the current device, enqueued on `stream` (a hipStream_t, null = the default
+ * stream); nothing is copied back in between, so the call returns before the kernels ran. d_sizes [ceil(n / 65280)] gets
+ * every member's length, the packed stream starts at d_out, which holds drm_bgzf_bound(n) bytes; d_work is scratch of at
+ * least *bytes of drm_bgzf_workspace(n) (64 KiB per block, plus 255 KiB for each of up to 512 workgroups). d_data, d_out,
+ * d_sizes and d_work must not overlap. The same argument errors, plus a null or too small workspace. */
+int drm_bgzf_block(void);
+int drm_bgzf_bound(int64_t n, size_t *bytes);
+int drm_bgzf_eof(uint8_t out[28]);
+int drm_bgzf_compress(const uint8_t *data, int64_t n, int device, uint8_t *out, size_t cap, size_t *bytes);
+int drm_bgzf_workspace(int64_t n, size_t *bytes);
+int drm_bgzf_compress_device(const uint8_t *d_data, int64_t n, uint8_t *d_out, uint32_t *d_sizes, void *d_work,
+                             size_t work_bytes, void *stream);
+/* The BAM bytes in front of compression (host only; SAMv1 sec. 4.2). Both write *bytes = the length even when cap is too
+ * small, which is DRM_ERR_ARG, as is a null pointer.
+ * drm_bam_header: "BAM\1", l_text, the text as given, n_ref, and for every line of the text that starts with "@SQ\t", in
+ * order, l_name (counting the NUL), the name from SN:, NUL, l_ref from LN:. An @SQ line without SN or LN: DRM_ERR_ARG.
+ * drm_bam_record: one SAM text line (a trailing newline is allowed) as one alignment record, block_size first.
+ *   refID, next_refID  the index of RNAME / RNEXT in ref_names; "*" gives -1, RNEXT "=" the line's own refID
+ *   pos, next_pos      POS - 1, PNEXT - 1 (0 in the text becomes -1)
+ *   bin                reg2bin(pos, pos + max(1, reference bases of the CIGAR)) of SAMv1 sec. 5.3 with arithmetic shifts
+ *                      (4680 for pos = -1), its low 16 bits
+ *   l_read_name        counts the NUL; a QNAME over 254 bytes is DRM_ERR_UNSUPPORTED
+ *   cigar              len << 4 | op over MIDNSHP=X; "*" = none
+ *   seq                4 bits a base over =ACMGRSVTWYHKDBN, high nibble first, any other character 15; "*" = l_seq 0
+ *   qual               the character minus 33; "*" = 0xFF for every base
+ *   tags               i: the smallest of C S I that holds a value >= 0, of c s i for a negative one (samtools' rule);
+ *                      Z: the text and a NUL; A: one byte; any other type is DRM_ERR_UNSUPPORTED
+ * DRM_ERR_ARG: fewer than eleven columns, a FLAG, POS, MAPQ, PNEXT, TLEN or i tag that is no number (or outside its
+ * field), a CIGAR that does not parse, a QUAL of another length than SEQ, an RNAME or RNEXT that is not among the names, a
+ * tag that is not XX:T:value. The SAM writers feed the same encoder the line they built, not its text. */
+int drm_bam_header(const char *sam_header_text, size_t len, uint8_t *out, size_t cap, size_t *bytes);
+int drm_bam_record(const char *line, size_t len, const char *const *ref_names, int32_t n_ref, uint8_t *out, size_t cap,
+                   size_t *bytes);
+
 /* ---------------------------------------------------------------- L2 rerank (the reference's live path)
  * post_process_l2_static (src/utils/post_processor.cpp:1023-1162, called at src/main.cpp:330) ->
  * find_sequences (static) -> Vectorizer::vectorize of the candidate windows -> batch_reranker(k = k_clusters)

@@ -55,6 +55,12 @@
 // run (a few hundred bytes per line); an external merge for runs that do not fit in host memory is not implemented.
 // DRM_SAM_STATS=1 prints the SAM stage's time and the rows it aligned, and with DRM_SAM_SORT the sort's and the final
 // write's time.
+// DRM_SAM_FORMAT=bam (with the same companions as DRM_SAM_SORT; sam or unset = the file as before, any other value is an
+// error) writes <output_dir>/results.bam and no results.sam: the BAM header of the same @HD / @SQ text, every line as a BAM
+// alignment record in the order the lines would have had (with DRM_SAM_SORT=coordinate the spool holds the records and
+// the sorted file is written from them), compressed as BGZF on the GPU (drm_bgzf_compress) in whole
+// 65,280-byte blocks with the tail carried across SAM blocks, so the file does not depend on DRM_SAM_BLOCK, and closed
+// by the empty EOF member. DRM_SAM_STATS=1 then also prints the bytes in and out of the compression and its time.
 // DRM_SAM_QUAL=1 keeps the quality lines of .fastq / .fq queries (and DRM_MATES) and prints them in column 11, reversed
 // on a line whose SEQ is reverse-complemented; a quality line of another length than its read ends the run.
 // Sequence inputs are embedded by the reference's GRU model on the GPU (drm_vectorize) when
@@ -521,6 +527,7 @@ struct Options {
     bool sam_stats = false; // DRM_SAM_STATS: one line with the SAM stage's time and the rows it aligned
     bool sam_dup = false;   // DRM_SAM_DUP: flag 1024 on the lines of a template whose 5' ends were seen before
     bool sam_sort = false;  // DRM_SAM_SORT=coordinate: the lines are held back and written in coordinate order
+    bool sam_bam = false;   // DRM_SAM_FORMAT=bam: results.bam (BAM records, BGZF from the device) instead of results.sam
     size_t sam_block = 0; // DRM_SAM_BLOCK, 0 = unset
 
     const AffineMode *affine() const { return has_affine ? &affine_mode : nullptr; }
@@ -625,6 +632,21 @@ static Options read_options(int argc, char *argv[], size_t ref_len, size_t strid
             throw drm::Error(DRM_ERR_ARG, "DRM_SAM_SORT=coordinate needs use_dynamic=1 use_streaming=1 DRM_SAM_CIGAR=1 "
                                           "and sequence queries: the keys are the lines' real RNAME and POS");
     }
+    // DRM_SAM_FORMAT=sam|bam, nothing else; checked like DRM_SAM_SORT, before the index is loaded
+    if (const char *e = std::getenv("DRM_SAM_FORMAT")) {
+        const std::string v = e;
+        if (v != "sam" && v != "bam")
+            throw drm::Error(DRM_ERR_ARG, "DRM_SAM_FORMAT must be sam or bam: " + quoted(v));
+        o.sam_bam = v == "bam";
+        if (o.sam_bam && !(use_dynamic && o.use_streaming && cigar && !o.is_npy))
+            throw drm::Error(DRM_ERR_ARG, "DRM_SAM_FORMAT=bam needs use_dynamic=1 use_streaming=1 DRM_SAM_CIGAR=1 and "
+                                          "sequence queries: the records hold the lines' real RNAME, POS and CIGAR");
+        if (o.sam_bam && o.devices.size() != 1)
+            throw drm::Error(DRM_ERR_UNSUPPORTED, "DRM_SAM_FORMAT=bam runs on one device (DRM_DEVICE), not on "
+                                                  "DRM_DEVICES");
+        if (o.sam_bam)
+            o.sam_file = o.out_dir + "/results.bam";
+    }
     if (!o.is_npy)
         o.model = drm::encoder_model_path();
 
@@ -651,6 +673,9 @@ static Options read_options(int argc, char *argv[], size_t ref_len, size_t strid
     o.sam_cigar = o.stream_sam && !o.header_only && cigar;
     if (o.sam_sort && (o.header_only || l2_rows))
         throw drm::Error(DRM_ERR_ARG, "DRM_SAM_SORT=coordinate does not go with a sparse index's header-only SAM or "
+                                      "DRM_SAM_L2_ROWS=1: those files are not written by the block loop");
+    if (o.sam_bam && (o.header_only || l2_rows))
+        throw drm::Error(DRM_ERR_ARG, "DRM_SAM_FORMAT=bam does not go with a sparse index's header-only SAM or "
                                       "DRM_SAM_L2_ROWS=1: those files are not written by the block loop");
     return o;
 }
@@ -740,6 +765,8 @@ struct Pipeline {
     drm_dupset *dups = nullptr; // DRM_SAM_DUP: the run's first-seen set, one item per pair or read (run)
     // DRM_SAM_SORT=coordinate: every line of the run with its key, filled by the writer thread block after block
     mutable drm::SamSpool spool;
+    // DRM_SAM_FORMAT=bam: the run's BAM file, fed by the writer thread block after block and closed by run()
+    mutable drm::BamFile bam;
     // DRM_SAM_STATS: the rows handed to the aligner and the time of the blocks' produce steps (everything between the
     // rerank and the writer thread: the locus scans, the alignments, the MD pass)
     size_t aligned_rows = 0;
@@ -748,6 +775,7 @@ struct Pipeline {
     explicit Pipeline(const Options &opt)
         : o(opt), k((size_t)opt.k), kc((size_t)opt.k_clusters), device(opt.devices[0]), pair_prm(opt.pair.prm)
     {
+        bam.device = device;
     }
 
     // false: a sequence file without a record
@@ -973,6 +1001,7 @@ struct Pipeline {
         b.quals = &quals;
         b.q0 = q0;
         b.spool = o.sam_sort ? &spool : nullptr;
+        b.bam = o.sam_bam ? &bam : nullptr;
         return b;
     }
 
@@ -1528,7 +1557,10 @@ struct Pipeline {
         const drm::SamContigs sc{&ctable, nullptr};
         drm::SamBlock b = sam_block(0);
         b.ctg = o.contigs ? &sc : nullptr;
-        drm::write_sam_sorted(b, spool, order.data());
+        if (o.sam_bam)
+            drm::write_bam_sorted(b, spool, order.data());
+        else
+            drm::write_sam_sorted(b, spool, order.data());
         if (o.sam_stats)
             std::cout << "[MAIN] SAM sort: " << n << " lines, " << sort_ms << " ms for the order (copies included), "
                       << std::chrono::duration<double, std::milli>(clk::now() - t0).count()
@@ -1569,6 +1601,11 @@ struct Pipeline {
                       << " ms for the block loop" << std::endl;
         if (rc == DRM_OK && o.sam_sort)
             write_sorted_sam();
+        else if (rc == DRM_OK && o.sam_bam) // after the last block: the remainder and the EOF member
+            bam.finish();
+        if (rc == DRM_OK && o.sam_bam && o.sam_stats)
+            std::cout << "[MAIN] BAM compression: " << bam.bytes_in << " bytes in, " << bam.bytes_out << " bytes out, "
+                      << bam.compress_ms << " ms in drm_bgzf_compress" << std::endl;
         return rc;
     }
 
